@@ -12,6 +12,10 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with two extra o
                  launch stream around each launch, in an instrumented step after the timed region).
   cpu_baseline — the CPU oracle (a port of the reference's PyTorch path) timed on the host cores on a
                  bounded sample (ViT-B/32, batch 32, fp32 full train steps), rank 0 at N=1 only.
+
+--dump-outputs DIR writes what the last timed step computed on rank 0 as DIR/<name>.npy (float32): `loss`, every tensor of the
+model's output dict, and `param.<name>` / `grad.<name>` for every parameter after the optimizer step.  Inputs and init are seeded,
+so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -32,6 +36,9 @@ sys.path.insert(0, ROOT)
 PEAK_BF16_DENSE_TFLOPS = 2500.0      # MI355X_MICROARCH.md: ~2.5 PF dense bf16 MFMA
 PEAK_FP8_DENSE_TFLOPS = 5000.0       # MI355X_MICROARCH.md: ~5 PF dense fp8 MFMA
 FWD_BWD_GFLOP_PER_PAIR = {"ViT-B-32": 44.3, "ViT-B-16": 123.3, "ViT-L-14-336": 1185.7, "ViT-H-14": 1145.0}
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_OUTPUT_ELEMS = 1 << 21          # a model output up to this size is written whole (ViT-B/32 at batch 4096: 4096 x 512)
+DUMP_PARAM_ELEMS = 4096              # per parameter and per gradient
 
 
 def parse():
@@ -63,7 +70,12 @@ def parse():
                    help="N > 1 ranks that SHARE device 0 over gloo (RCCL refuses two ranks on one device): runs the exact N > 1 "
                         "bench path -- per-rank batch shard, feature gather in the loss, gradient hooks -- on a one-GPU box "
                         "(tests/test_two_ranks_gpu.py); its timings mean nothing")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="write the outputs of the last timed step as DIR/<name>.npy (rank 0), for comparing two builds")
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 class LaunchTimer:
@@ -201,6 +213,33 @@ def host_cores():
     return max(1, n)
 
 
+def _flat_sample(t, k):
+    """`t` as float32 on the host; above k elements a fixed, seeded sample of k of them, flattened (the indices depend only on
+    t.numel(), so the same sample is taken from every build)."""
+    t = t.detach()
+    if t.numel() > k:
+        idx = torch.randint(0, t.numel(), (k,), generator=torch.Generator().manual_seed(0)).sort().values
+        t = t.reshape(-1)[idx.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(path, loss, out, model):
+    """What a caller of the train step holds after it: the loss, the model's outputs, the updated parameters and their gradients."""
+    import numpy as np
+    arrays = {"loss": _flat_sample(loss, 1)}
+    arrays.update({k: _flat_sample(v, DUMP_OUTPUT_ELEMS) for k, v in out.items() if isinstance(v, torch.Tensor)})
+    for name, p in model.named_parameters():
+        arrays["param." + name] = _flat_sample(p, DUMP_PARAM_ELEMS)
+        if p.grad is not None:
+            arrays["grad." + name] = _flat_sample(p.grad, DUMP_PARAM_ELEMS)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed {DUMP_LIMIT_BYTES}"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    print(f"[bench] wrote {len(arrays)} arrays ({total / 2**20:.1f} MiB) to {path}", file=sys.stderr, flush=True)
+
+
 def cpu_model():
     try:
         with open("/proc/cpuinfo") as f:
@@ -319,7 +358,9 @@ def main():
     sched = cosine_lr(opt, 5e-4, 2000, 200000)
     counter = {"n": 0}
 
-    def step():
+    last_out = {}           # the model outputs of the last timed step, for --dump-outputs
+
+    def step(keep_out=False):
         sched(counter["n"])
         counter["n"] += 1
         opt.zero_grad(set_to_none=True)
@@ -330,6 +371,8 @@ def main():
         sync.wait()
         opt.step()
         ops.clamp1(model.logit_scale.data, 0.0, math.log(100))
+        if keep_out:
+            last_out.update(out)
         return loss
 
     def fence():
@@ -344,8 +387,8 @@ def main():
             first_loss = float(loss.detach())
     fence()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(keep_out=bool(args.dump_outputs) and i == args.steps - 1)
     dt_host = time.perf_counter() - t0          # the host's share: every launch of the K steps is queued at this point
     fence()
     dt = time.perf_counter() - t0
@@ -359,6 +402,9 @@ def main():
         assert final_loss != first_loss, "the loss did not move: the optimizer step is not reaching the weights"
         assert abs(final_loss - math.log(args.global_batch)) > 1e-3 or abs(first_loss - math.log(args.global_batch)) < 1e-3, \
             "the model collapsed to uniform logits (loss = ln N)"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, last_out, model)
+    last_out.clear()
     ms = dt / args.steps * 1e3
     ips = args.global_batch / (dt / args.steps)
     layout = model._text_engine.last_layout

@@ -327,20 +327,25 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(int rows, int width, const 
             }
         }
     }
-    // fold the 4 waves through LDS (float atomics on LDS), then one partial row per block
+    // fold the 4 waves through LDS one wave at a time (a fixed summation order: the same partials every run), then one
+    // partial row per block
+    for (int w = 0; w < 4; ++w) {
+        if (wave == w) {
 #pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int ch = lane + 64 * i;
-        if (ch < nch) {
-            float* a = red + 4 * ch;
-            atomicAdd(a + 0, pg[i].x); atomicAdd(a + 1, pg[i].y); atomicAdd(a + 2, pg[i].z); atomicAdd(a + 3, pg[i].w);
-            a = red + width + 4 * ch;
-            atomicAdd(a + 0, pb[i].x); atomicAdd(a + 1, pb[i].y); atomicAdd(a + 2, pb[i].z); atomicAdd(a + 3, pb[i].w);
-            a = red + 2 * width + 4 * ch;
-            atomicAdd(a + 0, pc[i].x); atomicAdd(a + 1, pc[i].y); atomicAdd(a + 2, pc[i].z); atomicAdd(a + 3, pc[i].w);
+            for (int i = 0; i < NCH; ++i) {
+                const int ch = lane + 64 * i;
+                if (ch < nch) {
+                    float* a = red + 4 * ch;
+                    a[0] += pg[i].x; a[1] += pg[i].y; a[2] += pg[i].z; a[3] += pg[i].w;
+                    a = red + width + 4 * ch;
+                    a[0] += pb[i].x; a[1] += pb[i].y; a[2] += pb[i].z; a[3] += pb[i].w;
+                    a = red + 2 * width + 4 * ch;
+                    a[0] += pc[i].x; a[1] += pc[i].y; a[2] += pc[i].z; a[3] += pc[i].w;
+                }
+            }
         }
+        __syncthreads();
     }
-    __syncthreads();
     float* out = ws + (long)blockIdx.x * 3 * width;
     for (int i = threadIdx.x; i < 3 * width; i += 256) out[i] = red[i];
     // a launch with fewer than LN_BWD_BLOCKS blocks zero-fills the partial rows nobody owns
@@ -767,27 +772,21 @@ extern "C" int clipx_vision_assemble(int dtype, int batch, int tokens, int width
     return 0;
 }
 
-// out[j] += sum_b in[b*n + j]  (batch split over gridDim.y, fp32 atomics: <= BSUM_PARTS adders/address)
+// ws[part*n + j] = sum_{b in part} in[b*n + j]: the batch split over gridDim.y parts of `per` rows (every part non-empty); the
+// launcher adds the parts up in part order (no atomics: the same sums every run)
 #define BSUM_PARTS 64
 template <typename T>
-__global__ void batchsum_kernel(int batch, int n, const T* __restrict__ in, float* __restrict__ out,
-                                float* __restrict__ out2, int n2) {
+__global__ void batchsum_kernel(int batch, int per, int n, const T* __restrict__ in, float* __restrict__ ws) {
     const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (j >= n) return;
-    const int per = (batch + BSUM_PARTS - 1) / BSUM_PARTS;
     const int b0 = blockIdx.y * per;
-    int b1 = b0 + per;
-    if (b1 > batch) b1 = batch;
-    if (b0 >= b1) return;
+    const int b1 = min(b0 + per, batch);
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int b = b0; b < b1; ++b) {
         const float4 v = load4(in + (long)b * n + j);
         s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
     }
-    atomicAdd(out + j, s.x); atomicAdd(out + j + 1, s.y); atomicAdd(out + j + 2, s.z); atomicAdd(out + j + 3, s.w);
-    if (out2 && j < n2) {   // class-embedding gradient == first positional row's sum
-        atomicAdd(out2 + j, s.x); atomicAdd(out2 + j + 1, s.y); atomicAdd(out2 + j + 2, s.z); atomicAdd(out2 + j + 3, s.w);
-    }
+    store4(ws + (long)blockIdx.y * n + j, s);
 }
 
 template <typename T>
@@ -806,17 +805,27 @@ __global__ void vision_unassemble_kernel(int batch, int tokens, int width, const
 
 extern "C" int clipx_scale(size_t n, float* x, float s, void* stream);
 
+extern "C" size_t clipx_vision_assemble_bwd_ws_bytes(int tokens, int width) {
+    return (size_t)BSUM_PARTS * tokens * width * sizeof(float);
+}
+
 extern "C" int clipx_vision_assemble_bwd(int dtype, int batch, int tokens, int width, const void* dx0,
-                                         void* dtok, float* dpos, float* dcls, float beta, void* stream) {
+                                         void* dtok, float* dpos, float* dcls, float beta, float* ws, size_t ws_bytes,
+                                         void* stream) {
     CLIPX_CHECK(width % 4 == 0, "assemble_bwd: width %% 4");
+    CLIPX_CHECK(ws_bytes >= clipx_vision_assemble_bwd_ws_bytes(tokens, width), "assemble_bwd: workspace too small");
     const int n = tokens * width;
-    if (beta == 0.f) {
-        (void)hipMemsetAsync(dpos, 0, sizeof(float) * n, (hipStream_t)stream);
-        (void)hipMemsetAsync(dcls, 0, sizeof(float) * width, (hipStream_t)stream);
-    } else if (beta != 1.f) {
-        clipx_scale(n, dpos, beta, stream);
-        clipx_scale(width, dcls, beta, stream);
+    if (batch <= 0) {
+        if (beta == 0.f) {
+            (void)hipMemsetAsync(dpos, 0, sizeof(float) * n, (hipStream_t)stream);
+            (void)hipMemsetAsync(dcls, 0, sizeof(float) * width, (hipStream_t)stream);
+        } else if (beta != 1.f) {
+            clipx_scale(n, dpos, beta, stream);
+            clipx_scale(width, dcls, beta, stream);
+        }
+        return 0;
     }
+    const int per = cdiv(batch, BSUM_PARTS), nparts = cdiv(batch, per);
     const long total = (long)batch * (tokens - 1) * (width / 4);
     int grid = (int)((total + 255) / 256);
     if (grid > 65536) grid = 65536;
@@ -824,9 +833,12 @@ extern "C" int clipx_vision_assemble_bwd(int dtype, int batch, int tokens, int w
         if (dtok)
             hipLaunchKernelGGL(vision_unassemble_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, batch, tokens,
                                width, (const T*)dx0, (T*)dtok);
-        hipLaunchKernelGGL(batchsum_kernel<T>, dim3(cdiv(n, 1024), BSUM_PARTS), dim3(256), 0, (hipStream_t)stream, batch,
-                           n, (const T*)dx0, dpos, dcls, width);
+        hipLaunchKernelGGL(batchsum_kernel<T>, dim3(cdiv(n, 1024), nparts), dim3(256), 0, (hipStream_t)stream, batch, per,
+                           n, (const T*)dx0, ws);
     });
+    // dpos = beta*dpos + sum of the parts; the class-embedding gradient is the first positional row's sum
+    launch_reduce_partials(nparts, n, n, ws, dpos, beta, (hipStream_t)stream);
+    launch_reduce_partials(nparts, width, n, ws, dcls, beta, (hipStream_t)stream);
     CLIPX_LAUNCH_CHECK();
     return 0;
 }
@@ -863,19 +875,44 @@ extern "C" int clipx_text_embed(int dtype, int batch, int L, int width, int voca
     return 0;
 }
 
+// The token rows are summed in 64-bit fixed point: integer atomics add up to the same bits in any order, so the gradient
+// is the same every run (fp32 atomics were not), and text_embed_fix_finish_kernel rounds each exact sum to fp32 once.
+// The scale is 2^shift with shift = 58 - ceil(log2(rows)): contributions |v| < TE_FIX_MAX from at most `rows` rows sum to
+// less than 2^62, so nothing can overflow (2^-40 resolution at 176k rows, finer for fewer).  A contribution that is not
+// finite or not below TE_FIX_MAX is added to dtable in fp32 as before, so NaN / inf still reach the gradient.
+#define TE_FIX_MAX 16.0f
+static int te_fix_shift(long rows) {
+    int l = 0;
+    while ((1L << l) < rows) ++l;
+    return 58 - l;
+}
+__device__ __forceinline__ void te_fix_add(unsigned long long* fix, float* dtable, float v, float scale) {
+    if (fabsf(v) < TE_FIX_MAX) atomicAdd(fix, (unsigned long long)__float2ll_rn(v * scale));
+    else atomicAdd(dtable, v);
+}
+__global__ __launch_bounds__(256) void text_embed_fix_finish_kernel(long n, const unsigned long long* __restrict__ fix,
+                                                                    double inv_scale, float* __restrict__ dtable) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const long long q = (long long)fix[i];
+        if (q != 0) dtable[i] += (float)((double)q * inv_scale);
+    }
+}
+
 // embedding backward: one wave per token row; rows whose gradient is exactly zero (everything
 // behind the EOT token under the causal mask) issue no atomics.
 template <typename T>
 __global__ __launch_bounds__(256) void text_embed_bwd_kernel(int rows, int width, int vocab,
                                                              const int64_t* __restrict__ text,
                                                              const T* __restrict__ dx0,
+                                                             unsigned long long* __restrict__ fix, float scale,
                                                              float* __restrict__ dtable) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int r = blockIdx.x * 4 + wave; r < rows; r += gridDim.x * 4) {
         const T* g = dx0 + (long)r * width;
         long tokid = text[r];
         tokid = tokid < 0 ? 0 : (tokid >= vocab ? vocab - 1 : tokid);
-        float* dst = dtable + tokid * width;
+        unsigned long long* dst = fix + tokid * width;
+        float* dst_f = dtable + tokid * width;
         for (int c0 = 0; c0 < width; c0 += 256) {
             float v[4];
             bool nz = false;
@@ -889,27 +926,47 @@ __global__ __launch_bounds__(256) void text_embed_bwd_kernel(int rows, int width
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int c = c0 + 64 * j + lane;
-                    if (c < width) atomicAdd(dst + c, v[j]);
+                    if (c < width && v[j] != 0.f) te_fix_add(dst + c, dst_f + c, v[j], scale);
                 }
             }
         }
     }
 }
 
+extern "C" size_t clipx_text_embed_bwd_ws_bytes(int L, int width, int vocab) {
+    return (size_t)vocab * width * sizeof(unsigned long long) + (size_t)BSUM_PARTS * L * width * sizeof(float);
+}
 extern "C" int clipx_text_embed_bwd(int dtype, int batch, int L, int width, int vocab, const int64_t* text,
-                                    const void* dx0, float* dtable, float* dpos, float beta, void* stream) {
+                                    const void* dx0, float* dtable, float* dpos, float beta, void* ws, size_t ws_bytes,
+                                    void* stream) {
     CLIPX_CHECK(width % 4 == 0, "text_embed_bwd: width %% 4");
+    CLIPX_CHECK(ws_bytes >= clipx_text_embed_bwd_ws_bytes(L, width, vocab), "text_embed_bwd: workspace too small");
     const int rows = batch * L, n = L * width;
-    if (beta == 0.f) (void)hipMemsetAsync(dpos, 0, sizeof(float) * n, (hipStream_t)stream);
-    else if (beta != 1.f) clipx_scale(n, dpos, beta, stream);
+    if (batch <= 0) {
+        if (beta == 0.f) (void)hipMemsetAsync(dpos, 0, sizeof(float) * n, (hipStream_t)stream);
+        else if (beta != 1.f) clipx_scale(n, dpos, beta, stream);
+        return 0;
+    }
+    const int per = cdiv(batch, BSUM_PARTS), nparts = cdiv(batch, per);
+    unsigned long long* fix = (unsigned long long*)ws;
+    float* parts = (float*)(fix + (size_t)vocab * width);
+    const long ntab = (long)vocab * width;
+    (void)hipMemsetAsync(fix, 0, sizeof(unsigned long long) * ntab, (hipStream_t)stream);
+    const int shift = te_fix_shift(rows);
+    const float scale = ldexpf(1.f, shift);
     int grid = cdiv(rows, 4);
     if (grid > 16384) grid = 16384;
     DISPATCH_T(dtype, {
         hipLaunchKernelGGL(text_embed_bwd_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, rows, width, vocab,
-                           text, (const T*)dx0, dtable);
-        hipLaunchKernelGGL(batchsum_kernel<T>, dim3(cdiv(n, 1024), BSUM_PARTS), dim3(256), 0, (hipStream_t)stream, batch,
-                           n, (const T*)dx0, dpos, (float*)nullptr, 0);
+                           text, (const T*)dx0, fix, scale, dtable);
+        hipLaunchKernelGGL(batchsum_kernel<T>, dim3(cdiv(n, 1024), nparts), dim3(256), 0, (hipStream_t)stream, batch, per,
+                           n, (const T*)dx0, parts);
     });
+    int fgrid = cdiv(ntab, 256);
+    if (fgrid > 8192) fgrid = 8192;
+    hipLaunchKernelGGL(text_embed_fix_finish_kernel, dim3(fgrid), dim3(256), 0, (hipStream_t)stream, ntab, fix,
+                       ldexp(1.0, -shift), dtable);
+    launch_reduce_partials(nparts, n, n, parts, dpos, beta, (hipStream_t)stream);
     CLIPX_LAUNCH_CHECK();
     return 0;
 }
@@ -1111,15 +1168,17 @@ extern "C" int clipx_text_embed_packed(int dtype, int rows, int width, const int
     return 0;
 }
 
-// backward: dtable[row_tok[r]] += dx0[r] (fp32 atomics, all-zero rows skipped) and
+// backward: dtable[row_tok[r]] += dx0[r] and
 // dpos[t] = beta*dpos[t] + sum over sequences s with len > t of dx0[cu[s] + t]
 template <typename T>
 __global__ __launch_bounds__(256) void text_embed_packed_bwd_kernel(int rows, int width, const int* __restrict__ row_tok,
-                                                                    const T* __restrict__ dx0, float* __restrict__ dtable) {
+                                                                    const T* __restrict__ dx0, unsigned long long* __restrict__ fix,
+                                                                    float scale, float* __restrict__ dtable) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int r = blockIdx.x * 4 + wave; r < rows; r += gridDim.x * 4) {
         const T* g = dx0 + (long)r * width;
-        float* dst = dtable + (long)row_tok[r] * width;
+        unsigned long long* dst = fix + (long)row_tok[r] * width;
+        float* dst_f = dtable + (long)row_tok[r] * width;
         for (int c0 = 0; c0 < width; c0 += 256) {
             float v[4];
             bool nz = false;
@@ -1133,7 +1192,7 @@ __global__ __launch_bounds__(256) void text_embed_packed_bwd_kernel(int rows, in
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int c = c0 + 64 * j + lane;
-                    if (c < width) atomicAdd(dst + c, v[j]);
+                    if (c < width && v[j] != 0.f) te_fix_add(dst + c, dst_f + c, v[j], scale);
                 }
             }
         }
@@ -1142,8 +1201,9 @@ __global__ __launch_bounds__(256) void text_embed_packed_bwd_kernel(int rows, in
 #define TP_PARTS 16
 template <typename T>
 __global__ __launch_bounds__(256) void text_pos_grad_kernel(int nseq, int width, const int* __restrict__ cu,
-                                                            const T* __restrict__ dx0, float* __restrict__ dpos) {
-    // block (t, part): position t, sequences part, part + TP_PARTS, ...; thread = 4 columns
+                                                            const T* __restrict__ dx0, float* __restrict__ ws) {
+    // block (t, part): position t, sequences part, part + TP_PARTS, ...; thread = 4 columns; ws[part][t][c], summed over the
+    // parts in part order by the launcher
     const int t = blockIdx.x, part = blockIdx.y;
     for (int c = threadIdx.x * 4; c < width; c += blockDim.x * 4) {
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1154,25 +1214,42 @@ __global__ __launch_bounds__(256) void text_pos_grad_kernel(int nseq, int width,
                 acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
             }
         }
-        float* d = dpos + (long)t * width + c;
-        atomicAdd(d, acc.x); atomicAdd(d + 1, acc.y); atomicAdd(d + 2, acc.z); atomicAdd(d + 3, acc.w);
+        store4(ws + ((long)part * gridDim.x + t) * width + c, acc);
     }
 }
-extern "C" int clipx_text_embed_packed_bwd(int dtype, int rows, int nseq, int L, int width, const int* row_tok, const int* cu,
-                                           const void* dx0, float* dtable, float* dpos, float beta, void* stream) {
+extern "C" size_t clipx_text_embed_packed_bwd_ws_bytes(int L, int width, int vocab) {
+    return (size_t)vocab * width * sizeof(unsigned long long) + (size_t)TP_PARTS * L * width * sizeof(float);
+}
+extern "C" int clipx_text_embed_packed_bwd(int dtype, int rows, int nseq, int L, int width, int vocab, const int* row_tok,
+                                           const int* cu, const void* dx0, float* dtable, float* dpos, float beta, void* ws,
+                                           size_t ws_bytes, void* stream) {
     CLIPX_CHECK(width % 4 == 0, "text_embed_packed_bwd: width %% 4");
+    CLIPX_CHECK(ws_bytes >= clipx_text_embed_packed_bwd_ws_bytes(L, width, vocab), "text_embed_packed_bwd: workspace too small");
     const int n = L * width;
-    if (beta == 0.f) (void)hipMemsetAsync(dpos, 0, sizeof(float) * n, (hipStream_t)stream);
-    else if (beta != 1.f) clipx_scale(n, dpos, beta, stream);
-    if (rows <= 0) return 0;
+    if (rows <= 0) {
+        if (beta == 0.f) (void)hipMemsetAsync(dpos, 0, sizeof(float) * n, (hipStream_t)stream);
+        else if (beta != 1.f) clipx_scale(n, dpos, beta, stream);
+        return 0;
+    }
+    unsigned long long* fix = (unsigned long long*)ws;
+    float* parts = (float*)(fix + (size_t)vocab * width);
+    const long ntab = (long)vocab * width;
+    (void)hipMemsetAsync(fix, 0, sizeof(unsigned long long) * ntab, (hipStream_t)stream);
+    const int shift = te_fix_shift(rows);
+    const float scale = ldexpf(1.f, shift);
     int grid = cdiv(rows, 4);
     if (grid > 16384) grid = 16384;
     DISPATCH_T(dtype, {
         hipLaunchKernelGGL(text_embed_packed_bwd_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, rows, width,
-                           row_tok, (const T*)dx0, dtable);
+                           row_tok, (const T*)dx0, fix, scale, dtable);
         hipLaunchKernelGGL(text_pos_grad_kernel<T>, dim3(L, TP_PARTS), dim3(256), 0, (hipStream_t)stream, nseq, width, cu,
-                           (const T*)dx0, dpos);
+                           (const T*)dx0, parts);
     });
+    int fgrid = cdiv(ntab, 256);
+    if (fgrid > 8192) fgrid = 8192;
+    hipLaunchKernelGGL(text_embed_fix_finish_kernel, dim3(fgrid), dim3(256), 0, (hipStream_t)stream, ntab, fix,
+                       ldexp(1.0, -shift), dtable);
+    launch_reduce_partials(TP_PARTS, n, n, parts, dpos, beta, (hipStream_t)stream);
     CLIPX_LAUNCH_CHECK();
     return 0;
 }

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256) void ce_fused_fwd_kernel(int np, int nq, int E
 __global__ __launch_bounds__(256) void ce_fused_merge_kernel(int n, int ntiles, const float* __restrict__ part_m,
                                                              const float* __restrict__ part_l,
                                                              const float* __restrict__ zdiag, float weight,
-                                                             float* __restrict__ lse, float* __restrict__ loss_acc) {
+                                                             float* __restrict__ lse, float* __restrict__ loss_part) {
     __shared__ float part[4];
     const int i = blockIdx.x * 256 + threadIdx.x;
     float contrib = 0.f;
@@ -127,13 +127,21 @@ __global__ __launch_bounds__(256) void ce_fused_merge_kernel(int n, int ntiles, 
     contrib = wave_sum(contrib);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = contrib;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(loss_acc, weight * ((part[0] + part[1]) + (part[2] + part[3])));
+    if (threadIdx.x == 0) loss_part[blockIdx.x] = weight * ((part[0] + part[1]) + (part[2] + part[3]));
+}
+
+// *acc += sum_i part[i] in index order (one thread: the block partials of a loss or d(scale) add up the same way every run)
+__global__ void ce_sum_parts_kernel(int n, const float* __restrict__ part, float* __restrict__ acc) {
+    float s = 0.f;
+    for (int i = 0; i < n; ++i) s += part[i];
+    *acc += s;
 }
 
 extern "C" size_t clipx_ce_fused_ws_bytes(int np, int nq, int symmetric) {
     const size_t tq = (nq + LF_T - 1) / LF_T, tp = (np + LF_T - 1) / LF_T;
     size_t f = 2 * tq * (size_t)np + (size_t)max(np, nq);                 // row partials + label logits
     if (symmetric) f += 2 * tp * (size_t)nq;
+    f += (size_t)cdiv(np, 256) + (symmetric ? (size_t)cdiv(nq, 256) : 0);   // loss partials of the merge blocks
     return f * sizeof(float);
 }
 
@@ -150,13 +158,16 @@ extern "C" int clipx_ce_fused_fwd(int np, int nq, int E, const float* P, const f
     float* zdiag = row_l + (size_t)tq * np;
     float* col_m = zdiag + max(np, nq);
     float* col_l = col_m + (size_t)tp * nq;
+    float* loss_part = symmetric ? col_l + (size_t)tp * nq : col_m;     // after the last partials in use
     hipLaunchKernelGGL(ce_fused_fwd_kernel, dim3(tq, tp), dim3(256), 0, (hipStream_t)stream, np, nq, E, P, Q, label_off,
                        symmetric, row_m, row_l, symmetric ? col_m : nullptr, symmetric ? col_l : nullptr, zdiag);
     hipLaunchKernelGGL(ce_fused_merge_kernel, dim3(cdiv(np, 256)), dim3(256), 0, (hipStream_t)stream, np, tq, row_m, row_l,
-                       zdiag, w_own, lse_own, loss_acc);
+                       zdiag, w_own, lse_own, loss_part);
     if (symmetric)
         hipLaunchKernelGGL(ce_fused_merge_kernel, dim3(cdiv(nq, 256)), dim3(256), 0, (hipStream_t)stream, nq, tp, col_m,
-                           col_l, zdiag, w_oth, lse_oth, loss_acc);
+                           col_l, zdiag, w_oth, lse_oth, loss_part + cdiv(np, 256));
+    hipLaunchKernelGGL(ce_sum_parts_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream,
+                       cdiv(np, 256) + (symmetric ? cdiv(nq, 256) : 0), loss_part, loss_acc);
     CLIPX_LAUNCH_CHECK();
     return 0;
 }
@@ -171,7 +182,7 @@ __global__ __launch_bounds__(256, (NE <= 32 ? 2 : 1)) void ce_fused_bwd_kernel(i
                                                            float w_own, int off_own, const float* __restrict__ lse_oth,
                                                            float w_oth, int off_oth, const float* __restrict__ out_scale_dev,
                                                            float out_scale_mul, const float* __restrict__ gout_dev,
-                                                           float* __restrict__ dP, float* __restrict__ dscale_acc,
+                                                           float* __restrict__ dP_part, float* __restrict__ ds_part_out,
                                                            const float* __restrict__ scale_dev) {
     constexpr int E = 16 * NE;
     constexpr int EC = (NE >= 4) ? 64 : 16 * NE;     // columns of Q staged per chunk of the product
@@ -259,7 +270,8 @@ __global__ __launch_bounds__(256, (NE <= 32 ? 2 : 1)) void ce_fused_bwd_kernel(i
         }
         __syncthreads();
     }
-    // ---- write-out: dP += out_scale * acc  (atomics: the walk over q tiles is split over gridDim.y blocks)
+    // ---- write-out: this block's share of dP (the walk over q tiles is split over gridDim.y blocks): dP_part[blockIdx.y][p][e],
+    // summed over the splits in split order by ce_split_sum_kernel (no atomics: the same dP every run)
     float osc = out_scale_mul;
     if (out_scale_dev) osc *= out_scale_dev[0];
     if (gout_dev) osc *= gout_dev[0];
@@ -268,27 +280,58 @@ __global__ __launch_bounds__(256, (NE <= 32 ? 2 : 1)) void ce_fused_bwd_kernel(i
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int p = prow[r];
-            if (p < np) atomicAdd(dP + (long)p * E + 16 * t + c, osc * acc[t][r]);
+            if (p < np) dP_part[((long)blockIdx.y * np + p) * E + 16 * t + c] = osc * acc[t][r];
         }
-    if (dscale_acc) {
+    if (ds_part_out) {
         ds_part = wave_sum(ds_part);
         if (lane == 0) red[wave] = ds_part;
         __syncthreads();
-        if (tid == 0) atomicAdd(dscale_acc, ((red[0] + red[1]) + (red[2] + red[3])) / scale_dev[0]);
+        if (tid == 0)
+            ds_part_out[blockIdx.y * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) / scale_dev[0];
     }
+}
+
+// out[j] = sum_s part[s*n + j], s in order
+__global__ __launch_bounds__(256) void ce_split_sum_kernel(int nsplit, long n, const float* __restrict__ part,
+                                                           float* __restrict__ out) {
+    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < n; j += (long)gridDim.x * 256) {
+        float s = 0.f;
+        for (int k = 0; k < nsplit; ++k) s += part[k * n + j];
+        out[j] = s;
+    }
+}
+
+// blocks over the q tiles of one row tile: ~3 blocks per CU in flight
+static int ce_bwd_split(int np, int nq) {
+    const int tp = cdiv(np, LF_T), tq = cdiv(nq, LF_T);
+    int split = cdiv(768, tp);
+    if (split > tq) split = tq;
+    if (split < 1) split = 1;
+    return split;
+}
+
+extern "C" size_t clipx_ce_fused_bwd_ws_bytes(int np, int nq, int E) {
+    const size_t split = ce_bwd_split(np, nq);
+    return (split * (size_t)np * E + split * (size_t)cdiv(np, LF_T)) * sizeof(float);
 }
 
 template <int NE>
 static int launch_ce_bwd(int np, int nq, const float* P, const float* Q, const float* lse_own, float w_own, int off_own,
                          const float* lse_oth, float w_oth, int off_oth, const float* out_scale_dev, float out_scale_mul,
-                         const float* gout_dev, float* dP, float* dscale_acc, const float* scale_dev, hipStream_t stream) {
-    const int tp = cdiv(np, LF_T), tq = cdiv(nq, LF_T);
-    int split = cdiv(768, tp);                     // ~3 blocks per CU in flight
-    if (split > tq) split = tq;
-    if (split < 1) split = 1;
-    (void)hipMemsetAsync(dP, 0, sizeof(float) * (size_t)np * 16 * NE, stream);
+                         const float* gout_dev, float* dP, float* dscale_acc, const float* scale_dev, float* ws,
+                         hipStream_t stream) {
+    const int tp = cdiv(np, LF_T);
+    const int split = ce_bwd_split(np, nq);
+    const long n = (long)np * 16 * NE;
+    float* dP_part = ws;
+    float* ds_part = ws + (size_t)split * n;
     hipLaunchKernelGGL(ce_fused_bwd_kernel<NE>, dim3(tp, split), dim3(256), 0, stream, np, nq, P, Q, lse_own, w_own, off_own,
-                       lse_oth, w_oth, off_oth, out_scale_dev, out_scale_mul, gout_dev, dP, dscale_acc, scale_dev);
+                       lse_oth, w_oth, off_oth, out_scale_dev, out_scale_mul, gout_dev, dP_part,
+                       dscale_acc ? ds_part : nullptr, scale_dev);
+    int grid = cdiv(n, 256);
+    if (grid > 8192) grid = 8192;
+    hipLaunchKernelGGL(ce_split_sum_kernel, dim3(grid), dim3(256), 0, stream, split, n, dP_part, dP);
+    if (dscale_acc) hipLaunchKernelGGL(ce_sum_parts_kernel, dim3(1), dim3(1), 0, stream, tp * split, ds_part, dscale_acc);
     CLIPX_LAUNCH_CHECK();
     return 0;
 }
@@ -296,14 +339,15 @@ static int launch_ce_bwd(int np, int nq, const float* P, const float* Q, const f
 extern "C" int clipx_ce_fused_bwd(int np, int nq, int E, const float* P, const float* Q, const float* lse_own, float w_own,
                                   int off_own, const float* lse_oth, float w_oth, int off_oth, const float* out_scale_dev,
                                   float out_scale_mul, const float* gout_dev, float* dP, float* dscale_acc,
-                                  const float* scale_dev, void* stream) {
+                                  const float* scale_dev, void* ws, size_t ws_bytes, void* stream) {
     CLIPX_CHECK(np > 0 && nq > 0, "ce_fused_bwd: empty problem");
+    CLIPX_CHECK(ws_bytes >= clipx_ce_fused_bwd_ws_bytes(np, nq, E), "ce_fused_bwd: workspace too small");
     CLIPX_CHECK(lse_own || lse_oth, "ce_fused_bwd: no cross-entropy term");
     CLIPX_CHECK(!dscale_acc || scale_dev, "ce_fused_bwd: d(scale) needs the scale");
 #define LF_CASE(ne)                                                                                                     \
     if (E == 16 * (ne))                                                                                                 \
         return launch_ce_bwd<ne>(np, nq, P, Q, lse_own, w_own, off_own, lse_oth, w_oth, off_oth, out_scale_dev,         \
-                                 out_scale_mul, gout_dev, dP, dscale_acc, scale_dev, (hipStream_t)stream);
+                                 out_scale_mul, gout_dev, dP, dscale_acc, scale_dev, (float*)ws, (hipStream_t)stream);
     LF_CASE(1) LF_CASE(2) LF_CASE(4) LF_CASE(8) LF_CASE(16) LF_CASE(32) LF_CASE(40) LF_CASE(48) LF_CASE(64)
 #undef LF_CASE
     clipx_set_error("ce_fused_bwd: embed dim %d unsupported (16, 32, 64, 128, 256, 512, 640, 768, 1024)", E);

@@ -403,8 +403,10 @@ def vision_assemble(tok, cls, pos, batch, tokens):
 def vision_assemble_bwd(dx0, batch, tokens, dpos, dcls, beta):
     width = dx0.shape[-1]
     dtok = torch.empty((batch * (tokens - 1), width), dtype=dx0.dtype, device=dx0.device)
+    nbytes = int(_lib.lib().clipx_vision_assemble_bwd_ws_bytes(tokens, width))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dx0.device)
     check(_lib.lib().clipx_vision_assemble_bwd(dt_code(dx0.dtype), batch, tokens, width, _p(_c(dx0)), _p(dtok),
-                                               _p(dpos), _p(dcls), float(beta), _stream()))
+                                               _p(dpos), _p(dcls), float(beta), _p(ws), nbytes, _stream()))
     return dtok
 
 
@@ -423,8 +425,10 @@ def text_embed(text, table, pos, dtype):
 def text_embed_bwd(text, dx0, dtable, dpos, beta):
     b, L = text.shape
     vocab, width = dtable.shape
+    nbytes = int(_lib.lib().clipx_text_embed_bwd_ws_bytes(L, width, vocab))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dx0.device)
     check(_lib.lib().clipx_text_embed_bwd(dt_code(dx0.dtype), b, L, width, vocab, _p(_c(text)), _p(_c(dx0)),
-                                          _p(dtable), _p(dpos), float(beta), _stream()))
+                                          _p(dtable), _p(dpos), float(beta), _p(ws), nbytes, _stream()))
 
 
 def gather_rows(src, row_index):
@@ -494,9 +498,11 @@ def text_embed_packed(layout, table, pos, dtype):
 @family("embed")
 def text_embed_packed_bwd(layout, dx0, dtable, dpos, beta):
     vocab, width = dtable.shape
-    check(_lib.lib().clipx_text_embed_packed_bwd(dt_code(dx0.dtype), layout.rows, layout.nseq, layout.L, width,
+    nbytes = int(_lib.lib().clipx_text_embed_packed_bwd_ws_bytes(layout.L, width, vocab))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dx0.device)
+    check(_lib.lib().clipx_text_embed_packed_bwd(dt_code(dx0.dtype), layout.rows, layout.nseq, layout.L, width, vocab,
                                                  _p(layout.row_tok), _p(layout.cu), _p(_c(dx0)), _p(dtable), _p(dpos),
-                                                 float(beta), _stream()))
+                                                 float(beta), _p(ws), nbytes, _stream()))
 
 
 def eot_index(text):
@@ -571,9 +577,11 @@ def ce_fused_bwd(P, Q, lse_own, w_own, off_own, lse_oth, w_oth, off_oth, out_sca
                  scale_dev=None):
     np_, E = P.shape
     dP = torch.empty((np_, E), dtype=torch.float32, device=P.device)
+    nbytes = int(_lib.lib().clipx_ce_fused_bwd_ws_bytes(np_, Q.shape[0], E))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=P.device)
     check(_lib.lib().clipx_ce_fused_bwd(np_, Q.shape[0], E, _p(_c(P)), _p(_c(Q)), _p(lse_own), float(w_own), int(off_own),
                                         _p(lse_oth), float(w_oth), int(off_oth), _p(out_scale_dev), 1.0, _p(gout_dev),
-                                        _p(dP), _p(dscale_acc), _p(scale_dev), _stream()))
+                                        _p(dP), _p(dscale_acc), _p(scale_dev), _p(ws), nbytes, _stream()))
     return dP
 
 

@@ -153,16 +153,21 @@ int clipx_patchify(int img_dtype, int dtype, int batch, int H, int W, int P, int
 int clipx_vision_assemble(int dtype, int batch, int tokens, int width, const void* tok,
                           const float* cls, const float* pos, void* x0, void* stream);
 /* backward: dtok[b*G2+g] = dx0[b,1+g]; dpos[l] = beta*dpos[l] + sum_b dx0[b,l];
- * dcls = beta*dcls + sum_b dx0[b,0].                                                    */
+ * dcls = beta*dcls + sum_b dx0[b,0].  ws: clipx_vision_assemble_bwd_ws_bytes() bytes (partial sums over batch parts,
+ * added in a fixed order: the same result every run).                                  */
+size_t clipx_vision_assemble_bwd_ws_bytes(int tokens, int width);
 int clipx_vision_assemble_bwd(int dtype, int batch, int tokens, int width, const void* dx0,
-                              void* dtok, float* dpos, float* dcls, float beta, void* stream);
+                              void* dtok, float* dpos, float* dcls, float beta, float* ws, size_t ws_bytes, void* stream);
 /* x0[b,l] = table[text[b,l]] + pos[l]   (transformer.py:980,988; text int64)             */
 int clipx_text_embed(int dtype, int batch, int L, int width, int vocab, const int64_t* text,
                      const float* table, const float* pos, void* x0, void* stream);
-/* dtable[text[b,l]] += dx0[b,l] (fp32 atomics, all-zero rows skipped);
- * dpos[l] = beta*dpos[l] + sum_b dx0[b,l].  dtable must already hold beta*dtable.        */
+/* dtable[text[b,l]] += dx0[b,l] (finite contributions below 16 in magnitude are summed in 64-bit fixed point, exact for
+ * |v| >= 2^-40 at 176k rows, and rounded to fp32 once; others, NaN / inf included, are added in fp32; all-zero rows skipped);
+ * dpos[l] = beta*dpos[l] + sum_b dx0[b,l].  dtable must already hold beta*dtable.  Both the same every run.
+ * ws: clipx_text_embed_bwd_ws_bytes() bytes of scratch.                                  */
+size_t clipx_text_embed_bwd_ws_bytes(int L, int width, int vocab);
 int clipx_text_embed_bwd(int dtype, int batch, int L, int width, int vocab, const int64_t* text,
-                         const void* dx0, float* dtable, float* dpos, float beta, void* stream);
+                         const void* dx0, float* dtable, float* dpos, float beta, void* ws, size_t ws_bytes, void* stream);
 /* ---- row gather / scatter: only the pooled token of each sample leaves the last residual block (`x[:, 0]` transformer.py:695,
  * `x[arange, text.argmax(-1)]` :851), so the block's out_proj / MLP and their backward run on `batch` rows.
  * gather: dst[r] = src[row_index[r]];  scatter: dst (dst_rows x width) = 0 then dst[row_index[r]] = src[r], or with
@@ -184,10 +189,13 @@ int clipx_text_layout(int batch, int L, int vocab, int row_align, const int64_t*
 /* x0[r] = table[row_tok[r]] + pos[row_pos[r]]  (transformer.py:980,988 on the packed rows)                               */
 int clipx_text_embed_packed(int dtype, int rows, int width, const int* row_tok, const int* row_pos,
                             const float* table, const float* pos, void* x0, void* stream);
-/* dtable[row_tok[r]] += dx0[r] (atomics, zero rows skipped; dtable holds beta*dtable already);
- * dpos[t] = beta*dpos[t] + sum_{s: len_s > t} dx0[cu[s] + t]                                                              */
-int clipx_text_embed_packed_bwd(int dtype, int rows, int nseq, int L, int width, const int* row_tok, const int* cu,
-                                const void* dx0, float* dtable, float* dpos, float beta, void* stream);
+/* dtable[row_tok[r]] += dx0[r] (summed like clipx_text_embed_bwd; zero rows skipped; dtable holds
+ * beta*dtable already); dpos[t] = beta*dpos[t] + sum_{s: len_s > t} dx0[cu[s] + t].  Both the same every run.
+ * ws: clipx_text_embed_packed_bwd_ws_bytes() bytes of scratch.                                                            */
+size_t clipx_text_embed_packed_bwd_ws_bytes(int L, int width, int vocab);
+int clipx_text_embed_packed_bwd(int dtype, int rows, int nseq, int L, int width, int vocab, const int* row_tok,
+                                const int* cu, const void* dx0, float* dtable, float* dpos, float beta, void* ws,
+                                size_t ws_bytes, void* stream);
 /* idx[s] = cu[s+1] - 1: the EOT (pooled) row of caption s in the packed layout                                            */
 int clipx_packed_eot_index(int batch, const int* cu, int* idx, void* stream);
 /* idx[b] = b*L + argmax_l text[b,l] (first maximum; transformer.py:851)                  */
@@ -224,13 +232,15 @@ int clipx_ce_fused_fwd(int np, int nq, int E, const float* P, const float* Q, in
                        float w_own, float w_oth, float* lse_own, float* lse_oth, float* loss_acc, void* ws,
                        size_t ws_bytes, void* stream);
 /* bwd of one operand, logits recomputed tile by tile:  dP[p,:] = osc * sum_q dz(p,q) * Q[q,:],
+ * ws: clipx_ce_fused_bwd_ws_bytes() bytes (partials of the blocks that split the q walk, summed in a fixed order),
  *   dz(p,q) = w_own*(exp(z - lse_own[p]) - [q == p+off_own]) + w_oth*(exp(z - lse_oth[q]) - [p == q+off_oth])
  * (a NULL lse pointer drops its term), osc = out_scale_mul * (*out_scale_dev if given) * (*gout_dev if given);
  * dscale_acc (optional) += sum dz*z / *scale_dev.  E in {16,32,64,128,256,512,640,768,1024}.                             */
+size_t clipx_ce_fused_bwd_ws_bytes(int np, int nq, int E);
 int clipx_ce_fused_bwd(int np, int nq, int E, const float* P, const float* Q, const float* lse_own, float w_own,
                        int off_own, const float* lse_oth, float w_oth, int off_oth, const float* out_scale_dev,
                        float out_scale_mul, const float* gout_dev, float* dP, float* dscale_acc,
-                       const float* scale_dev, void* stream);
+                       const float* scale_dev, void* ws, size_t ws_bytes, void* stream);
 /* out[i] = x[i] * (*s_dev): `logit_scale * image_features` with the scale left on the device
  * (loss.py:145-152 multiplies the features first, then takes the matmul).                    */
 int clipx_scale_by_dev(size_t n, const float* x, const float* s_dev, float* out, void* stream);

@@ -615,7 +615,97 @@ def golden_colxlip(T, L, tag):
     save(f"{tag}_batch{batch}.npz", **arrs)
 
 
+SEAM_SIGNATURES = [
+    ("colxlip/factory.py", None, "create_model"),
+    ("colxlip/factory.py", None, "create_model_and_transforms"),
+    ("colxlip/factory.py", None, "create_loss"),
+    ("colxlip/factory.py", None, "get_tokenizer"),
+    ("colxlip/factory.py", None, "load_checkpoint"),
+    ("colxlip/factory.py", None, "load_state_dict"),
+    ("colxlip/loss.py", None, "gather_features"),
+    ("colxlip/loss.py", None, "compute_colbert_similarity"),
+    ("colxlip/loss.py", "ClipLoss", "__init__"),
+    ("colxlip/loss.py", "ClipLoss", "get_ground_truth"),
+    ("colxlip/loss.py", "ClipLoss", "get_logits"),
+    ("colxlip/loss.py", "ClipLoss", "forward"),
+    ("colxlip/loss.py", "ColClipLoss", "__init__"),
+    ("colxlip/train.py", None, "train_one_epoch"),
+    ("colxlip/train.py", None, "evaluate"),
+    ("colxlip/train.py", None, "compute_retrieval"),
+    ("colxlip/train.py", None, "retrieval_on_split"),
+    ("colxlip/data.py", None, "get_data"),
+    ("colxlip/params.py", None, "parse_args"),
+    ("colxlip/model.py", None, "convert_weights_to_lp"),
+    ("colxlip/model.py", None, "get_cast_dtype"),
+    ("colxlip/model.py", None, "get_input_dtype"),
+]
+
+
+def golden_seam():
+    """what the reference's entry point imports from `colxlip`, which `args.<flag>` its main() and train loop read
+    and set, and the parameter lists of the functions it calls -- read from the reference's files with `ast` (nothing is
+    executed) and stored as names only, so that tests/test_seam_cpu.py checks the seam without the reference present."""
+    import ast
+    import json
+    src = os.path.dirname(REF)
+
+    def tree(rel):
+        with open(os.path.join(src, rel)) as f:
+            return ast.parse(f.read())
+
+    def func(t, name, cls=None):
+        body = t.body
+        if cls is not None:
+            body = next(n for n in body if isinstance(n, ast.ClassDef) and n.name == cls).body
+        return next(n for n in body if isinstance(n, ast.FunctionDef) and n.name == name)
+
+    def args_attrs(node, ctx):
+        return sorted({n.attr for n in ast.walk(node) if isinstance(n, ast.Attribute) and isinstance(n.value, ast.Name)
+                       and n.value.id == "args" and isinstance(n.ctx, ctx)})
+
+    def literal_defaults(fn):
+        out = {}
+        for name, node in zip(reversed([x.arg for x in fn.args.args]), reversed(fn.args.defaults)):
+            try:
+                ast.literal_eval(node)
+            except ValueError:
+                continue          # torch.float16 etc.
+            out[name] = ast.unparse(node)
+        return out
+
+    main_tree = tree("main.py")
+    main_fn = func(main_tree, "main")
+    train_tree = tree("colxlip/train.py")
+    seam = {
+        "main_colxlip_imports": [{"module": n.module, "names": [a.name for a in n.names], "line": n.lineno}
+                                 for n in ast.walk(main_tree)
+                                 if isinstance(n, ast.ImportFrom) and n.module and n.module.split(".")[0] == "colxlip"],
+        "root_exports": [a.name for n in ast.walk(tree("colxlip/__init__.py")) if isinstance(n, ast.ImportFrom) for a in n.names],
+        "main_args_read": args_attrs(main_fn, ast.Load),
+        "main_args_set": args_attrs(main_fn, ast.Store),
+        "train_args_read": {fn: args_attrs(func(train_tree, fn), ast.Load)
+                            for fn in ("train_one_epoch", "evaluate", "retrieval_on_split")},
+        "signatures": {},
+    }
+    for rel, cls, fn in SEAM_SIGNATURES:
+        node = func(tree(rel), fn, cls)
+        a = node.args
+        seam["signatures"][f"{rel}:{cls + '.' if cls else ''}{fn}"] = {
+            "params": [x.arg for x in a.posonlyargs + a.args + a.kwonlyargs],
+            "var_keyword": a.kwarg is not None,
+            "literal_defaults": literal_defaults(node),
+        }
+    path = os.path.join(HERE, "seam.json")
+    with open(path, "w") as f:
+        json.dump(seam, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(f"wrote seam.json: {os.path.getsize(path) / 1024:.1f} KiB")
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["seam"]:       # text only: nothing of the reference is imported
+        golden_seam()
+        sys.exit(0)
     torch.manual_seed(0)
     torch.set_num_threads(8)
     T, L = import_reference()

@@ -92,8 +92,7 @@ def test_train_step_with_gradsync_on_rccl(nccl_world1):
 
     a, b = run(False), run(True)
     assert all(math.isfinite(v) for v in b)
-    # same arithmetic with and without the synchroniser.  Not bit for bit: the text-embedding backward scatters with fp32
-    # atomics (clipx_text_embed_bwd), so the token-embedding gradient depends on arrival order from run to run
+    # same arithmetic with and without the synchroniser
     assert all(abs(x - y) <= 1e-4 * max(1.0, abs(x)) for x, y in zip(a, b)), (a, b)
 
 

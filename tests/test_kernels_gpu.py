@@ -816,6 +816,53 @@ def test_text_embed_packed(dtype):
     assert relerr(dpos, 2 * ref_p) < 1e-5
 
 
+@pytest.mark.parametrize("packed", [False, True])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_text_embed_bwd_token_sums(packed, dtype):
+    """The token-embedding gradient at the magnitudes of training (columns of 1e-9 .. 1e-3 per row; the EOT token on every
+    caption, the pad token on ~half the dense rows) against a float64 sum.  The 64-bit fixed-point sum is exact up to half a
+    step of 2^-(58 - ceil(log2 rows)) per contribution and is rounded to fp32 once; a second run gives the same bits; a NaN, an
+    inf and a contribution of 1e7 (beyond the fixed-point range) still reach the gradient."""
+    b, L, width, vocab = 300, 77, 128, 300
+    text, _ = _captions(b, L, vocab, seed=9)
+    text = text.to(DEV)
+    if packed:
+        lay = ops.TextLayout(text, vocab)
+        rows, tok = lay.rows, lay.row_tok[:lay.rows].long()
+    else:
+        rows, tok = b * L, text.reshape(-1)
+    g = torch.Generator().manual_seed(5)
+    mag = 10.0 ** torch.empty(1, width).uniform_(-9, -3, generator=g)
+    dx0 = (torch.randn(rows, width, generator=g) * mag).to(dtype).to(DEV)
+    if packed:
+        dx0[lay.rows_live:] = 0
+
+    def run(d):
+        dtable = torch.zeros(vocab, width, device=DEV)
+        dpos = torch.zeros(L, width, device=DEV)
+        if packed:
+            ops.text_embed_packed_bwd(lay, d, dtable, dpos, 0.0)
+        else:
+            ops.text_embed_bwd(text, d, dtable, dpos, 0.0)
+        return dtable
+
+    got = run(dx0)
+    assert torch.equal(got, run(dx0))
+    ref = torch.zeros(vocab, width, dtype=torch.float64, device=DEV).index_add_(0, tok, dx0.double())
+    count = torch.zeros(vocab, dtype=torch.float64, device=DEV).index_add_(0, tok, torch.ones(rows, dtype=torch.float64,
+                                                                                          device=DEV)).unsqueeze(1)
+    step = 2.0 ** -(58 - math.ceil(math.log2(rows)))
+    err = (got.double() - ref).abs()
+    assert bool((err <= ref.abs() * 2.0 ** -23 + count * step / 2).all()), float((err - ref.abs() * 2.0 ** -23).max())
+
+    special = dx0.clone()
+    special[0, 0], special[1, 1], special[2, 2] = float("nan"), float("inf"), 1e7
+    got = run(special)
+    ref = torch.zeros(vocab, width, dtype=torch.float64, device=DEV).index_add_(0, tok, special.double())
+    assert torch.isnan(got[tok[0], 0]) and torch.isinf(got[tok[1], 1]) and got[tok[1], 1] > 0
+    assert abs(float(got[tok[2], 2]) - float(ref[tok[2], 2])) <= 1e-6 * abs(float(ref[tok[2], 2]))
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("batch", [5, 300])
 def test_packed_attention_equals_padded(dtype, batch):

@@ -1,60 +1,37 @@
 """The Python seam: what the reference's entry point imports and reads must exist here under the same names.
 
-Half of these tests read `/root/reference/src/main.py` (and `colxlip/{__init__,factory,loss,train,data}.py`) AS TEXT with `ast`
-in the build container -- nothing of it is executed -- and are skipped where the reference is absent (the GPU box).  They
-prove exactly this, and INTEGRATION.md claims no more: with this repository on sys.path, every `from colxlip... import ...`
-of the reference's `main.py` resolves, every `args.<flag>` it reads is produced by `colxlip.params.parse_args`, by
-`init_distributed_device`, or by `main.py` itself, and the functions it calls take the arguments it passes.  `main.py`'s
-other imports (`open_clip_train.*`, `huggingface_hub`, `wandb`) are third-party packages of the reference's environment."""
+Half of these tests check against `tests/golden/seam.json`: names read with `ast` from the reference's `src/main.py` and
+`colxlip/{__init__,factory,loss,train,data,params,model}.py` (`make_golden.py seam`; nothing of it is executed and no source
+text is stored).  They prove exactly this, and INTEGRATION.md claims no more: with this repository on sys.path, every
+`from colxlip... import ...` of the reference's `main.py` resolves, every `args.<flag>` it reads is produced by
+`colxlip.params.parse_args`, by `init_distributed_device`, or by `main.py` itself, and the functions it calls take the
+arguments it passes.  `main.py`'s other imports (`open_clip_train.*`, `huggingface_hub`, `wandb`) are third-party packages of
+the reference's environment."""
 import ast
 import inspect
+import json
 import os
 
 import numpy as np
 import pytest
 import torch
 
-REF_SRC = "/root/reference/src"
-needs_reference = pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="reference checkout not present (GPU box)")
-
-
-def _tree(rel):
-    with open(os.path.join(REF_SRC, rel)) as f:
-        return ast.parse(f.read())
-
-
-def _func(tree, name, cls=None):
-    body = tree.body
-    if cls is not None:
-        body = next(n for n in body if isinstance(n, ast.ClassDef) and n.name == cls).body
-    return next(n for n in body if isinstance(n, ast.FunctionDef) and n.name == name)
-
-
-def _arg_names(fn):
-    a = fn.args
-    return [x.arg for x in a.posonlyargs + a.args + a.kwonlyargs]
-
-
-def _args_attrs(node, ctx):
-    return {n.attr for n in ast.walk(node)
-            if isinstance(n, ast.Attribute) and isinstance(n.value, ast.Name) and n.value.id == "args" and isinstance(n.ctx, ctx)}
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "seam.json")) as _f:
+    SEAM = json.load(_f)
 
 
 # ------------------------------------------------------------------ imports of the reference's main.py
-@needs_reference
 def test_every_colxlip_import_of_reference_main_resolves():
     import importlib
     seen = 0
-    for node in ast.walk(_tree("main.py")):
-        if isinstance(node, ast.ImportFrom) and node.module and node.module.split(".")[0] == "colxlip":
-            mod = importlib.import_module(node.module)
-            for alias in node.names:
-                assert hasattr(mod, alias.name), f"{node.module}.{alias.name} (main.py:{node.lineno}) does not exist here"
-                seen += 1
+    for node in SEAM["main_colxlip_imports"]:
+        mod = importlib.import_module(node["module"])
+        for name in node["names"]:
+            assert hasattr(mod, name), f"{node['module']}.{name} (main.py:{node['line']}) does not exist here"
+            seen += 1
     assert seen >= 7          # parse_args, create_model_and_transforms, get_tokenizer, create_loss, train_one_epoch, evaluate, get_data
 
 
-@needs_reference
 def test_colxlip_is_an_alias_not_a_copy():
     import colxlip
     import colxlip_amd
@@ -64,15 +41,12 @@ def test_colxlip_is_an_alias_not_a_copy():
         import colxlip.transformer  # noqa: F401  (no counterpart: absent on purpose)
 
 
-@needs_reference
 def test_reference_package_root_exports_exist():
     """Every name `src/colxlip/__init__.py` re-exports is importable from `colxlip` (a name whose subsystem is not built
     raises when CALLED, with a message; it is not silently missing)."""
     import colxlip
-    for node in ast.walk(_tree("colxlip/__init__.py")):
-        if isinstance(node, ast.ImportFrom):
-            for alias in node.names:
-                assert hasattr(colxlip, alias.name), alias.name
+    for name in SEAM["root_exports"]:
+        assert hasattr(colxlip, name), name
     with pytest.raises(NotImplementedError):
         colxlip.trace_model(None)
     with pytest.raises(RuntimeError):
@@ -90,12 +64,10 @@ def _provided_by_init_distributed_device():
     return set(vars(ns)) - before | {"device"}
 
 
-@needs_reference
 def test_every_flag_reference_main_reads_is_defined():
     from colxlip.params import parse_args
-    main_fn = _func(_tree("main.py"), "main")
-    reads = _args_attrs(main_fn, ast.Load)
-    own = _args_attrs(main_fn, ast.Store)                # args.name / log_path / wandb / checkpoint_path / save_logs / ...
+    reads = set(SEAM["main_args_read"])
+    own = set(SEAM["main_args_set"])                     # args.name / log_path / wandb / checkpoint_path / save_logs / ...
     parsed = set(vars(parse_args([])))
     dist = _provided_by_init_distributed_device()
     assert {"distributed", "rank", "local_rank", "world_size", "device"} <= dist
@@ -108,14 +80,11 @@ def test_every_flag_reference_main_reads_is_defined():
     assert d.remote_sync_frequency == 300 and d.remote_sync_protocol == "s3" and d.wandb_project_name == "open-clip"
 
 
-@needs_reference
 def test_flags_read_by_reference_train_loop_and_evaluate_are_defined():
     from colxlip.params import parse_args
-    tree = _tree("colxlip/train.py")
-    main_sets = _args_attrs(_func(_tree("main.py"), "main"), ast.Store)
-    parsed = set(vars(parse_args([]))) | _provided_by_init_distributed_device() | main_sets
+    parsed = set(vars(parse_args([]))) | _provided_by_init_distributed_device() | set(SEAM["main_args_set"])
     for fn_name in ("train_one_epoch", "evaluate", "retrieval_on_split"):
-        missing = sorted(_args_attrs(_func(tree, fn_name), ast.Load) - parsed)
+        missing = sorted(set(SEAM["train_args_read"][fn_name]) - parsed)
         assert not missing, (fn_name, missing)
 
 
@@ -139,7 +108,6 @@ def test_model_family_adam_defaults():
 
 
 # ------------------------------------------------------------------ call signatures
-@needs_reference
 @pytest.mark.parametrize("rel,cls,fn,ours", [
     ("colxlip/factory.py", None, "create_model", "colxlip.factory:create_model"),
     ("colxlip/factory.py", None, "create_model_and_transforms", "colxlip.factory:create_model_and_transforms"),
@@ -168,25 +136,21 @@ def test_signatures_accept_what_the_reference_passes(rel, cls, fn, ours):
     """Parameter names, in order, of the reference's definition are a prefix of ours (ours may add trailing keyword
     arguments with defaults: `grad_sync=` on train_one_epoch, `model=` on get_data), and the defaults agree."""
     import importlib
-    ref = _func(_tree(rel), fn, cls)
+    ref = SEAM["signatures"][f"{rel}:{cls + '.' if cls else ''}{fn}"]
     mod_name, _, path = ours.partition(":")
     obj = importlib.import_module(mod_name)
     for part in path.split("."):
         obj = getattr(obj, part)
     sig = inspect.signature(obj)
     mine = [p.name for p in sig.parameters.values() if p.kind not in (p.VAR_KEYWORD, p.VAR_POSITIONAL)]
-    want = _arg_names(ref)
+    want = ref["params"]
     assert mine[:len(want)] == want, (ours, want, mine)
     for extra in mine[len(want):]:
         assert sig.parameters[extra].default is not inspect.Parameter.empty, (ours, extra)
-    assert bool(ref.args.kwarg) == any(p.kind == p.VAR_KEYWORD for p in sig.parameters.values()), ours
-    # defaults: compare the literal ones
-    ref_defaults = dict(zip(reversed([x.arg for x in ref.args.args]), reversed(ref.args.defaults)))
-    for name, node in ref_defaults.items():
-        try:
-            val = ast.literal_eval(node)
-        except ValueError:
-            continue          # torch.float16 etc.
+    assert ref["var_keyword"] == any(p.kind == p.VAR_KEYWORD for p in sig.parameters.values()), ours
+    # defaults: compare the literal ones (the fixture keeps only those; torch.float16 etc. are left out)
+    for name, text in ref["literal_defaults"].items():
+        val = ast.literal_eval(text)
         assert sig.parameters[name].default == val, (ours, name, val, sig.parameters[name].default)
 
 
