@@ -17,7 +17,7 @@ from typing import Any, Dict, Optional, Tuple, Union
 import torch
 import torch.nn.functional as F
 
-from .loss import ClipLoss, ColClipLoss
+from .loss import ClipLoss, ColClipLoss, SigLipLoss
 from .model import CLIP, ColXLIP, get_cast_dtype, set_model_preprocess_cfg
 
 HF_HUB_PREFIX = 'hf-hub:'
@@ -411,13 +411,17 @@ def create_model_and_transforms(
 
 
 def create_loss(args):
-    """Loss module for `args.model` (boundary: reference factory.py:424-461): ColClipLoss for a colxlip model (global +
-    token-level MaxSim contrastive terms mixed by --alpha), ClipLoss otherwise; both cache their label vectors."""
+    """Loss module for `args.model` (boundary: reference factory.py:424-461): SigLipLoss under --siglip, ColClipLoss for a
+    colxlip model (global + token-level MaxSim contrastive terms mixed by --alpha), ClipLoss otherwise."""
     family = args.model.lower()
     if "coca" in family:
         raise NotImplementedError("CoCaLoss is outside the MI355X hot path")
     if getattr(args, "siglip", False):
-        raise NotImplementedError("SigLipLoss is outside the MI355X hot path")
+        # open_clip's trainer path (the reference's own create_loss reads a --loss-dist-impl its parser never defines)
+        assert not getattr(args, "horovod", False), "Horovod not currently supported for SigLip"
+        if "colxlip" in family:
+            raise ValueError("--siglip needs a CLIP model: a ColXLIP model's output carries token features SigLipLoss cannot take")
+        return SigLipLoss(rank=args.rank, world_size=args.world_size, dist_impl=getattr(args, "loss_dist_impl", None))
     if getattr(args, "distill_model", None):
         raise NotImplementedError("DistillClipLoss is outside the MI355X hot path")
     common = dict(local_loss=args.local_loss, gather_with_grad=args.gather_with_grad, cache_labels=True,

@@ -675,3 +675,303 @@ class ColClipLoss(nn.Module):
             return {"global_contrastive_loss": global_contrastive_loss, "token_contrastive_loss": token_contrastive_loss,
                     "total_loss": total_loss}
         return total_loss
+
+
+# --------------------------------------------------------------------------- SigLipLoss (reference loss.py:396-604)
+def _exchange_post(sends, recvs, group=None):
+    """Post one round of point-to-point transfers: sends [(tensor, to_rank)], recvs [(from_rank, like_tensor)].  Returns a
+    callable that waits and hands back the received device tensors in `recvs` order.  RCCL moves device tensors with
+    batch_isend_irecv; gloo stages them through host memory (its P2P on device tensors is not relied on)."""
+    from .distributed import backend_is_rccl
+    if backend_is_rccl(group):
+        out = [torch.empty_like(like) for _, like in recvs]
+        ops_ = [dist.P2POp(dist.isend, t.contiguous(), to, group=group) for t, to in sends]
+        ops_ += [dist.P2POp(dist.irecv, o, frm, group=group) for o, (frm, _) in zip(out, recvs)]
+        reqs = dist.batch_isend_irecv(ops_)
+
+        def wait():
+            for req in reqs:
+                req.wait()
+            return out
+        return wait
+    host_out = [torch.empty(like.shape, dtype=like.dtype) for _, like in recvs]
+    host_in = [t.detach().contiguous().cpu() for t, _ in sends]
+    reqs = [dist.isend(h, to, group=group) for h, (_, to) in zip(host_in, sends)]
+    reqs += [dist.irecv(h, frm, group=group) for h, (frm, _) in zip(host_out, recvs)]
+    devices = [like.device for _, like in recvs]
+
+    def wait():
+        for req in reqs:
+            req.wait()
+        return [h.to(d) for h, d in zip(host_out, devices)]
+    return wait
+
+
+def neighbour_exchange(from_rank, to_rank, tensor, group=None):
+    """reference loss.py:396-410: send `tensor` to `to_rank`, receive the same shape from `from_rank`."""
+    return _exchange_post([(tensor, to_rank)], [(from_rank, tensor)], group)()[0]
+
+
+def neighbour_exchange_bidir(left_rank, right_rank, tensor_to_left, tensor_to_right, group=None):
+    """reference loss.py:413-432: returns (tensor_from_right, tensor_from_left)."""
+    got = _exchange_post([(tensor_to_left, left_rank), (tensor_to_right, right_rank)],
+                         [(right_rank, tensor_to_left), (left_rank, tensor_to_right)], group)()
+    return got[0], got[1]
+
+
+class NeighbourExchange(torch.autograd.Function):
+    """reference loss.py:435-446: the gradient goes back to the rank the tensor came from."""
+
+    @staticmethod
+    def forward(ctx, from_rank, to_rank, group, tensor):
+        ctx.group, ctx.from_rank, ctx.to_rank = group, from_rank, to_rank
+        return neighbour_exchange(from_rank, to_rank, tensor, group=group)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return (None, None, None) + (NeighbourExchange.apply(ctx.to_rank, ctx.from_rank, ctx.group, grad_output),)
+
+
+def neighbour_exchange_with_grad(from_rank, to_rank, tensor, group=None):
+    return NeighbourExchange.apply(from_rank, to_rank, group, tensor)
+
+
+class NeighbourExchangeBidir(torch.autograd.Function):
+    """reference loss.py:453-464."""
+
+    @staticmethod
+    def forward(ctx, left_rank, right_rank, group, tensor_to_left, tensor_to_right):
+        ctx.group, ctx.left_rank, ctx.right_rank = group, left_rank, right_rank
+        return neighbour_exchange_bidir(left_rank, right_rank, tensor_to_left, tensor_to_right, group=group)
+
+    @staticmethod
+    def backward(ctx, *grad_outputs):
+        return (None, None, None) + NeighbourExchangeBidir.apply(ctx.right_rank, ctx.left_rank, ctx.group, *grad_outputs)
+
+
+def neighbour_exchange_bidir_with_grad(left_rank, right_rank, tensor_to_left, tensor_to_right, group=None):
+    return NeighbourExchangeBidir.apply(left_rank, right_rank, group, tensor_to_left, tensor_to_right)
+
+
+def _ring_rounds(rank, world_size, impl):
+    """The reference's exchange pattern (loss.py:527-584) as rounds of lanes (source block, to_rank, from_rank); block 0 is
+    this rank's own text features, every lane of a round appends the block it receives."""
+    right, left = (rank + 1) % world_size, (rank - 1 + world_size) % world_size
+    rounds = []
+    if impl == "shift":
+        for k in range(world_size - 1):
+            rounds.append([(k, right, left)])
+        return rounds
+    to_left = to_right = 0
+    num_bidir, remainder = divmod(world_size - 1, 2)
+    n = 1
+    for _ in range(num_bidir):
+        rounds.append([(to_left, left, right), (to_right, right, left)])   # receives (from_right, from_left)
+        to_left, to_right = n, n + 1
+        n += 2
+    if remainder:
+        rounds.append([(to_right, right, left)])
+    return rounds
+
+
+class _SigmoidBlocks:
+    """The per-block kernels: loss of z = scale * a @ blk.T + bias over one text block, with (fused dims) dA formed in the
+    forward walk or (other dims) the d(logits) matrix kept for the backward GEMMs."""
+
+    def __init__(self, a, scale, bias, inv_r, want_grad):
+        self.a, self.scale, self.bias, self.inv_r, self.want = a, scale, bias, inv_r, want_grad
+        self.fused = a.shape[1] in ops.FUSED_CE_DIMS
+        self.out3 = None
+        self.dA = None
+        self.dz = []                       # dense: d(logits) of every block, in forward order
+
+    def forward(self, blk, pos_off):
+        if self.fused:
+            self.out3, self.dA = ops.sigmoid_fused_fwd(self.a, blk, self.scale, self.bias, pos_off, self.inv_r, self.want,
+                                                       out3=self.out3, dA=self.dA)
+            return
+        r, e = self.a.shape
+        c = blk.shape[0]
+        z = torch.empty((r, c), dtype=torch.float32, device=self.a.device)
+        ops.gemm_f32(r, c, e, self.a, e, 1, blk, 1, e, z, c)
+        o3 = ops.sigmoid_dense(z, self.scale, self.bias, pos_off, self.inv_r)
+        self.out3 = o3 if self.out3 is None else self.out3 + o3
+        if self.want:
+            self.dz.append(z)
+
+    def grad_a(self, blocks, gout):
+        """dA * upstream (dense: every block's d(logits) @ block, scaled by scale * upstream)"""
+        if self.fused:
+            return ops.scale_by_dev(self.dA, gout)
+        r, e = self.a.shape
+        sg = self.scale * gout
+        da = torch.empty((r, e), dtype=torch.float32, device=self.a.device)
+        for i, (z, blk) in enumerate(zip(self.dz, blocks)):
+            ops.scale_by_dev(z, sg, out=z)
+            ops.gemm_f32(r, e, blk.shape[0], z, blk.shape[0], 1, blk, e, 1, da, e, 1.0, 0.0 if i == 0 else 1.0)
+        return da
+
+    def grad_block(self, i, blk, pos_off, gout, out=None):
+        """d(block i) * upstream; added to `out` when given.  Dense: after grad_a (the block's d(logits) already scaled)."""
+        if self.fused:
+            return ops.sigmoid_fused_bwd(self.a, blk, self.scale, self.bias, pos_off, self.inv_r, gout, dB=out,
+                                         accumulate=out is not None)
+        r, e = self.a.shape
+        c = blk.shape[0]
+        dst = out if out is not None else torch.empty((c, e), dtype=torch.float32, device=self.a.device)
+        ops.gemm_f32(c, e, r, self.dz[i], 1, c, self.a, e, 1, dst, e, 1.0, 1.0 if out is not None else 0.0)
+        return dst
+
+
+def _prep(a, b, scale, bias):
+    a = a.contiguous().float()
+    b = b.contiguous().float()
+    return a, b, scale.detach().float().reshape(1).contiguous(), bias.detach().float().reshape(1).contiguous()
+
+
+class _SigmoidLoss(torch.autograd.Function):
+    """SigLIP loss of one block: 1/r * sum softplus(-y z), z = scale * a @ b.T + bias, positives at column row + pos_off
+    (pos_off < 0: none).  The W == 1 case, and the gathered [b, W*b] block of dist_impl gather / reduce."""
+
+    @staticmethod
+    def forward(ctx, a, b, scale, bias, pos_off: int, want_grad: bool):
+        with phase("loss.fwd"):
+            a, b, s, bi = _prep(a, b, scale, bias)
+            k = _SigmoidBlocks(a, s, bi, 1.0 / a.shape[0], want_grad)
+            k.forward(b, pos_off)
+        ctx.k, ctx.b, ctx.pos_off = k, b, pos_off
+        ctx.shapes = (scale.shape, bias.shape)
+        return k.out3[0].clone().reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        k, b = ctx.k, ctx.b
+        with phase("loss.bwd"):
+            gout = gout.reshape(1).float().contiguous()
+            da = k.grad_a([b], gout)
+            db = k.grad_block(0, b, ctx.pos_off, gout) if ctx.needs_input_grad[1] else None
+            g2 = ops.scale_by_dev(k.out3[1:3].contiguous(), gout)
+        ctx.k = ctx.b = None
+        return (da if ctx.needs_input_grad[0] else None, db, g2[0].reshape(ctx.shapes[0]), g2[1].reshape(ctx.shapes[1]),
+                None, None)
+
+
+class _SigmoidRing(torch.autograd.Function):
+    """SigLIP loss with the text blocks passed around the ring (dist_impl shift / bidir, reference loss.py:524-570): the
+    next round's exchange is posted before the kernels on the current blocks run.  Backward: every received block's gradient
+    travels back along the path it came by, the next round's kernels running while it is in flight."""
+
+    @staticmethod
+    def forward(ctx, a, b, scale, bias, rank: int, world_size: int, impl: str, want_grad: bool):
+        a, b, s, bi = _prep(a, b, scale, bias)
+        rounds = _ring_rounds(rank, world_size, impl)
+        k = _SigmoidBlocks(a, s, bi, 1.0 / a.shape[0], want_grad)
+        blocks = [b]
+        with phase("loss.fwd"):
+            pending = _exchange_post([(blocks[src], to) for src, to, _ in rounds[0]], [(frm, b) for _, _, frm in rounds[0]])
+            k.forward(b, 0)
+            for j in range(len(rounds)):
+                got = pending()
+                blocks += got
+                if j + 1 < len(rounds):
+                    pending = _exchange_post([(blocks[src], to) for src, to, _ in rounds[j + 1]],
+                                             [(frm, b) for _, _, frm in rounds[j + 1]])
+                for blk in got:
+                    k.forward(blk, -1)
+        ctx.k, ctx.blocks, ctx.rounds = k, blocks, rounds
+        ctx.shapes = (scale.shape, bias.shape)
+        return k.out3[0].clone().reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        k, blocks, rounds = ctx.k, ctx.blocks, ctx.rounds
+        with phase("loss.bwd"):
+            gout = gout.reshape(1).float().contiguous()
+            da = k.grad_a(blocks, gout)
+            g = [None] * len(blocks)
+            # block index received by each lane of each round
+            recv_idx, n = [], 1
+            for lanes in rounds:
+                recv_idx.append(list(range(n, n + len(lanes))))
+                n += len(lanes)
+            pending, pend_lanes = None, None
+            for j in range(len(rounds) - 1, -1, -1):
+                for i in recv_idx[j]:                          # this round's received blocks (the sources of round j+1)
+                    g[i] = k.grad_block(i, blocks[i], -1, gout, out=g[i])
+                if pending is not None:
+                    for (src, _, _), t in zip(pend_lanes, pending()):
+                        g[src].add_(t)
+                # the gradient of every block received in round j goes back to its sender; what this rank sent comes back
+                pending = _exchange_post([(g[i], frm) for i, (_, _, frm) in zip(recv_idx[j], rounds[j])],
+                                         [(to, blocks[0]) for _, to, _ in rounds[j]])
+                pend_lanes = rounds[j]
+            g[0] = k.grad_block(0, blocks[0], 0, gout, out=g[0])
+            if pending is not None:
+                for (src, _, _), t in zip(pend_lanes, pending()):
+                    g[src].add_(t)
+            g2 = ops.scale_by_dev(k.out3[1:3].contiguous(), gout)
+        ctx.k = ctx.blocks = None
+        return da, g[0], g2[0].reshape(ctx.shapes[0]), g2[1].reshape(ctx.shapes[1]), None, None, None, None
+
+
+class SigLipLoss(nn.Module):
+    """Sigmoid Loss for Language Image Pre-Training (SigLIP) - https://arxiv.org/abs/2303.15343 (reference loss.py:470-604).
+
+    The loss runs in csrc/loss_sigmoid.hip (exact fp32, the logits recomputed tile by tile, 4 logits-GEMM equivalents per step).
+    dist_impl: `gather` / `reduce` all-gather the text features once (backward: reduce-scatter) and run ONE launch over the
+    [b, W*b] block with the positives at column rank*b -- the reference's sum of W block losses; `shift` / `bidir` pass the
+    text blocks around the ring with one launch per received block."""
+
+    def __init__(
+            self,
+            cache_labels: bool = False,
+            rank: int = 0,
+            world_size: int = 1,
+            dist_impl: Optional[str] = None,
+    ):
+        super().__init__()
+        self.cache_labels = cache_labels
+        self.rank = rank
+        self.world_size = world_size
+        self.dist_impl = dist_impl or 'bidir'  # default to bidir exchange, as the reference
+        assert self.dist_impl in ('bidir', 'shift', 'reduce', 'gather')
+
+        # cache state (unused, as in the reference)
+        self.prev_num_logits = 0
+        self.labels = {}
+
+    def get_ground_truth(self, device, dtype, num_logits, negative_only=False) -> torch.Tensor:
+        """The dense label matrix (API surface; the loss itself never forms it)."""
+        labels = -torch.ones((num_logits, num_logits), device=device, dtype=dtype)
+        if not negative_only:
+            labels = 2 * torch.eye(num_logits, device=device, dtype=dtype) + labels
+        return labels
+
+    def get_logits(self, image_features, text_features, logit_scale, logit_bias=None):
+        logits = _ScaledMatmul.apply(image_features, text_features, logit_scale)
+        if logit_bias is not None:
+            logits = logits + logit_bias
+        return logits
+
+    def _loss(self, image_features, text_features, logit_scale, logit_bias=None, negative_only=False):
+        if logit_bias is None:
+            logit_bias = torch.zeros((), dtype=torch.float32, device=image_features.device)
+        return _SigmoidLoss.apply(image_features, text_features, logit_scale, logit_bias, -1 if negative_only else 0,
+                                  self._want_grad(image_features, text_features, logit_scale, logit_bias))
+
+    @staticmethod
+    def _want_grad(*ts):
+        return torch.is_grad_enabled() and any(t.requires_grad for t in ts)
+
+    def forward(self, image_features, text_features, logit_scale, logit_bias, output_dict=False):
+        W = self.world_size
+        want = self._want_grad(image_features, text_features, logit_scale, logit_bias)
+        if W == 1:
+            loss = _SigmoidLoss.apply(image_features, text_features, logit_scale, logit_bias, 0, want)
+        elif self.dist_impl in ("gather", "reduce"):
+            b = image_features.shape[0]
+            all_text = _AllGatherCat.apply(text_features, self.rank, W) if want else _all_gather_nograd(text_features, W)
+            loss = _SigmoidLoss.apply(image_features, all_text, logit_scale, logit_bias, self.rank * b, want)
+        else:
+            loss = _SigmoidRing.apply(image_features, text_features, logit_scale, logit_bias, self.rank, W, self.dist_impl, want)
+        return {"contrastive_loss": loss} if output_dict else loss

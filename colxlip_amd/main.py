@@ -11,6 +11,7 @@ arenas (`--ddp-wrap` restores the literal DistributedDataParallel wrap), the opt
 here (`params.unsupported_flag_values`) stop the run with a message instead of being ignored."""
 import glob
 import logging
+import math
 import os
 import random
 import re
@@ -122,12 +123,16 @@ class _Run:
         if isinstance(a.force_image_size, (tuple, list)) and len(a.force_image_size) == 1:
             a.force_image_size = a.force_image_size[0]
         random_seed(a.seed, 0)                       # same initial weights on every rank
+        # EXTENSION: --siglip starts from open_clip's trainer values (the reference's main.py never sets a logit bias, so its
+        # SigLipLoss would get none); the bias is then a parameter like logit_scale (no weight decay by its name)
+        siglip_init = dict(init_logit_scale=math.log(10), init_logit_bias=-10.0) if getattr(a, "siglip", False) else {}
         self.core, self.pre_train, self.pre_val = create_model_and_transforms(
             a.model, a.pretrained, precision=a.precision, device=self.device, jit=a.torchscript,
             force_quick_gelu=a.force_quick_gelu, force_custom_text=a.force_custom_text,
             force_patch_dropout=a.force_patch_dropout, force_image_size=a.force_image_size,
             image_mean=a.image_mean, image_std=a.image_std, image_interpolation=a.image_interpolation,
-            image_resize_mode=a.image_resize_mode, aug_cfg=a.aug_cfg, pretrained_image=a.pretrained_image, output_dict=True)
+            image_resize_mode=a.image_resize_mode, aug_cfg=a.aug_cfg, pretrained_image=a.pretrained_image, output_dict=True,
+            **siglip_init)
         random_seed(a.seed, a.rank)
         if a.grad_checkpointing:
             self.core.set_grad_checkpointing()

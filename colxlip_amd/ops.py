@@ -585,6 +585,53 @@ def ce_fused_bwd(P, Q, lse_own, w_own, off_own, lse_oth, w_oth, off_oth, out_sca
     return dP
 
 
+@family("loss")
+def sigmoid_fused_fwd(A, B, scale_dev, bias_dev, pos_off, inv_r, want_grad, out3=None, dA=None):
+    """SigLIP loss of z = scale * A @ B.T + bias without z in memory.  Returns (out3 = [loss, d(scale), d(bias)], dA or None);
+    the gradients are at unit upstream gradient.  want_grad=False runs the loss-only walk.  Given out3 / dA are added to."""
+    r, E = A.shape
+    c = B.shape[0]
+    L = _lib.lib()
+    accumulate = out3 is not None
+    assert not accumulate or (dA is not None) == bool(want_grad)
+    nbytes = int(L.clipx_sigmoid_fused_ws_bytes(r, c, E, int(want_grad)))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=A.device)
+    if out3 is None:
+        out3 = torch.empty((3,), dtype=torch.float32, device=A.device)
+        dA = torch.empty((r, E), dtype=torch.float32, device=A.device) if want_grad else None
+    check(L.clipx_sigmoid_fused_fwd(r, c, E, _p(_c(A)), _p(_c(B)), _p(scale_dev), _p(bias_dev), int(pos_off), float(inv_r),
+                                    _p(out3), _p(dA), int(accumulate), _p(ws), nbytes, _stream()))
+    return out3, dA
+
+
+@family("loss")
+def sigmoid_fused_bwd(A, B, scale_dev, bias_dev, pos_off, inv_r, gout_dev, dB=None, accumulate=False):
+    """dB (+)= scale * upstream * dz.T @ A, the logits recomputed tile by tile."""
+    r, E = A.shape
+    c = B.shape[0]
+    if dB is None:
+        dB = torch.empty((c, E), dtype=torch.float32, device=A.device)
+    L = _lib.lib()
+    nbytes = int(L.clipx_sigmoid_fused_bwd_ws_bytes(r, c, E))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=A.device)
+    check(L.clipx_sigmoid_fused_bwd(r, c, E, _p(_c(A)), _p(_c(B)), _p(scale_dev), _p(bias_dev), int(pos_off), float(inv_r),
+                                    _p(gout_dev), _p(_c(dB)), int(accumulate), _p(ws), nbytes, _stream()))
+    return dB
+
+
+@family("loss")
+def sigmoid_dense(z, scale_dev, bias_dev, pos_off, inv_r):
+    """In place: dot products z -> d(logits); returns [loss, d(scale), d(bias)] (unit upstream gradient)."""
+    rows, cols = z.shape
+    L = _lib.lib()
+    nbytes = int(L.clipx_sigmoid_dense_ws_bytes(rows, cols))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=z.device)
+    out3 = torch.empty((3,), dtype=torch.float32, device=z.device)
+    check(L.clipx_sigmoid_dense(rows, cols, _p(z), z.stride(0), _p(scale_dev), _p(bias_dev), int(pos_off), float(inv_r),
+                                _p(out3), _p(ws), nbytes, _stream()))
+    return out3
+
+
 def scale_by_dev(x, s_dev, out=None):
     out = torch.empty_like(x) if out is None else out
     check(_lib.lib().clipx_scale_by_dev(x.numel(), _p(_c(x)), _p(s_dev), _p(out), _stream()))

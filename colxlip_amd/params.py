@@ -123,6 +123,8 @@ _FLAGS = {
     "--gather-with-grad": _flag(),
     "--alpha": dict(type=float, default=0.5),
     "--siglip": _flag(),
+    "--loss-dist-impl": dict(type=str, default=None, choices=["bidir", "shift", "reduce", "gather"],
+                             help="SigLipLoss's exchange of the text features between ranks (open_clip's flag; default bidir)"),
     # ---- distributed
     "--dist-url": dict(type=str, default="env://"),
     "--dist-backend": dict(type=str, default="nccl"),
@@ -143,7 +145,7 @@ _FLAGS = {
 _INERT_ONLY = {
     "remote_sync": None, "copy_codebase": False, "huggingface_model_name": "", "use_bnb_linear": None,
     "horovod": False, "torchscript": False, "trace": False, "lock_image": False, "lock_text": False,
-    "distill_model": None, "distill_pretrained": None, "inference_with_flair": False, "siglip": False,
+    "distill_model": None, "distill_pretrained": None, "inference_with_flair": False,
     "imagenet_val": None, "imagenet_v2": None, "use_bn_sync": False, "dataset_resampled": False,
     "torchcompile": False,        # no tracing compiler in this stack (hand-written kernels behind autograd Functions)
 }

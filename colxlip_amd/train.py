@@ -47,6 +47,14 @@ def unwrap_model(model):
     return getattr(model, "module", model)
 
 
+def _with_total(losses):
+    """The loss dict's sum is its total when it names none, as in open_clip's trainer: SigLipLoss returns only
+    `contrastive_loss` (reference loss.py:604), while the loop reads `total_loss` (reference train.py:135)."""
+    if "total_loss" not in losses:
+        losses["total_loss"] = sum(losses.values())
+    return losses
+
+
 def backward(total_loss, scaler=None):
     (scaler.scale(total_loss) if scaler is not None else total_loss).backward()
 
@@ -70,7 +78,7 @@ class _StepRunner:
     def _single(self, images, texts):
         out = self.model(images, texts)
         logit_scale = out["logit_scale"]
-        losses = self.loss(**out, output_dict=True)
+        losses = _with_total(self.loss(**out, output_dict=True))
         backward(losses["total_loss"], self.scaler)
         return losses, logit_scale
 
@@ -94,7 +102,7 @@ class _StepRunner:
                 scalars = {k: out.pop(k) for k in ("logit_scale", "logit_bias") if k in out}
                 logit_scale = scalars["logit_scale"]
                 feats = {key: torch.cat(vals[:j] + [out[key]] + vals[j + 1:]) for key, vals in cached.items()}
-                losses = self.loss(**feats, **scalars, output_dict=True)
+                losses = _with_total(self.loss(**feats, **scalars, output_dict=True))
                 backward(losses["total_loss"], self.scaler)
         return losses, logit_scale
 

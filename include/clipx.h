@@ -241,6 +241,27 @@ int clipx_ce_fused_bwd(int np, int nq, int E, const float* P, const float* Q, co
                        int off_own, const float* lse_oth, float w_oth, int off_oth, const float* out_scale_dev,
                        float out_scale_mul, const float* gout_dev, float* dP, float* dscale_acc,
                        const float* scale_dev, void* ws, size_t ws_bytes, void* stream);
+/* ---- SigLipLoss (loss.py:498-521): sigmoid contrastive loss WITHOUT the logits matrix in memory (exact-fp32 MFMA tiles).
+ *   z[i,j] = s*(A[i].B[j]) + beta, s = *scale_dev, beta = *bias_dev, A [r,E], B [c,E];
+ *   y = +1 where j == i + pos_off, -1 elsewhere (pos_off < 0: negatives only, loss.py:489-493);
+ *   loss = inv_r * sum softplus(-y z) (loss.py:508-516);  dz = -inv_r * y * sigmoid(-y z).
+ * fused_fwd: out3 = [loss, sum dz*(A.B), sum dz] (d(scale), d(bias) at unit upstream gradient);
+ *   dA = s * dz @ B (NULL: a loss-only walk, out3[1..2] = 0); accumulate != 0 adds to out3 and dA.  ws: clipx_sigmoid_fused_ws_bytes(r, c, E, dA != NULL) bytes.
+ * fused_bwd: dB (+)= s * (*gout_dev if given) * dz^T @ A  (accumulate != 0 adds to dB).  ws: clipx_sigmoid_fused_bwd_ws_bytes().
+ * Block and split partials are summed in a fixed order.  E in {16,32,64,128,256,512,640,768,1024}.                       */
+size_t clipx_sigmoid_fused_ws_bytes(int r, int c, int E, int grad);
+int clipx_sigmoid_fused_fwd(int r, int c, int E, const float* A, const float* B, const float* scale_dev,
+                            const float* bias_dev, int pos_off, float inv_r, float* out3, float* dA, int accumulate,
+                            void* ws, size_t ws_bytes, void* stream);
+size_t clipx_sigmoid_fused_bwd_ws_bytes(int r, int c, int E);
+int clipx_sigmoid_fused_bwd(int r, int c, int E, const float* A, const float* B, const float* scale_dev,
+                            const float* bias_dev, int pos_off, float inv_r, const float* gout_dev, float* dB,
+                            int accumulate, void* ws, size_t ws_bytes, void* stream);
+/* the same on a materialised dot matrix z[rows, cols] = A @ B^T (any embed dim): in place z -> dz,
+ * out3 = [loss, sum dz*z_in, sum dz].  ws: clipx_sigmoid_dense_ws_bytes() bytes.                                         */
+size_t clipx_sigmoid_dense_ws_bytes(int rows, int cols);
+int clipx_sigmoid_dense(int rows, int cols, float* z, long ldz, const float* scale_dev, const float* bias_dev,
+                        int pos_off, float inv_r, float* out3, void* ws, size_t ws_bytes, void* stream);
 /* out[i] = x[i] * (*s_dev): `logit_scale * image_features` with the scale left on the device
  * (loss.py:145-152 multiplies the features first, then takes the matmul).                    */
 int clipx_scale_by_dev(size_t n, const float* x, const float* s_dev, float* out, void* stream);
