@@ -17,6 +17,7 @@ ACT_NONE, ACT_GELU, ACT_QUICKGELU = 0, 1, 2
 
 _CTYPES = {
     "int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
+    "uint64_t": ctypes.c_uint64,
 }
 _lib = None
 

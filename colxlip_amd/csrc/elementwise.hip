@@ -503,7 +503,7 @@ __global__ __launch_bounds__(1024) void reduce_partials_kernel(int nparts, int n
         out[j] = (beta != 0.f ? beta * out[j] : 0.f) + t;
     }
 }
-static void launch_reduce_partials(int nparts, int n, long stride, const float* ws, float* out, float beta,
+void launch_reduce_partials(int nparts, int n, long stride, const float* ws, float* out, float beta,
                                    hipStream_t stream) {
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(cdiv(n, 64)), dim3(1024), 0, stream, nparts, n, stride, ws, out, beta);
 }

@@ -561,7 +561,7 @@ class _Engine:
         return out
 
     # -- one residual block -----------------------------------------------------------------
-    def _block_fwd(self, x, i: int, batch: int, layout=None, need_out: bool = True):
+    def _block_fwd(self, x, i: int, batch: int, L: int, layout=None, need_out: bool = True):
         P, pre = self.P, f"transformer.resblocks.{i}."
         a, mean1, rstd1, a8 = self._ln_fwd(x, pre + "ln_1.weight", pre + "ln_1.bias")
         qkv = self._lin(a, pre + "attn.in_proj_weight", P[pre + "attn.in_proj_bias"], q8=a8)
@@ -569,7 +569,7 @@ class _Engine:
             o = ops.attention_packed_fwd(qkv, layout, self.heads, self.causal)
         else:
             # (the online-softmax kernels hand their log-sum-exp to the backward: it rides on the saved output tensor)
-            o, lse = ops.attention_fwd(qkv, batch, self.seq, self.heads, self.causal, want_lse=True)
+            o, lse = ops.attention_fwd(qkv, batch, L, self.heads, self.causal, want_lse=True)
             o.clipx_lse = lse
         x1 = self._lin(o, pre + "attn.out_proj.weight", P[pre + "attn.out_proj.bias"], residual=x)
         c, mean2, rstd2, c8 = self._ln_fwd(x1, pre + "ln_2.weight", pre + "ln_2.bias")
@@ -599,7 +599,7 @@ class _Engine:
                 ops.layernorm_bwd_finish(width, ws, args[0], args[1], args[2], betas[k])
                 k += 1
 
-    def _block_bwd(self, dx2, saved, i: int, batch: int, prev_bias: Optional[str], layout=None):
+    def _block_bwd(self, dx2, saved, i: int, batch: int, L: int, prev_bias: Optional[str], layout=None):
         """dx2: grad of the block output.  The bias grad of this block's c_proj (= colsum(dx2)) was
         already produced by whoever made dx2.  Returns grad of the block input; colsum of it is
         folded into `prev_bias` (previous block's c_proj.bias) when given."""
@@ -645,7 +645,7 @@ class _Engine:
         if layout is not None:
             dqkv = ops.attention_packed_bwd(qkv, do, layout, self.heads, self.causal)
         else:
-            dqkv = ops.attention_bwd(qkv, do, batch, self.seq, self.heads, self.causal, out=o, lse=getattr(o, "clipx_lse", None))
+            dqkv = ops.attention_bwd(qkv, do, batch, L, self.heads, self.causal, out=o, lse=getattr(o, "clipx_lse", None))
         wgrad(dqkv, a, pre + "attn.in_proj_weight", pre + "attn.in_proj_bias")
         da = self._dgrad(dqkv, pre + "attn.in_proj_weight")
         dx0 = ops.layernorm_bwd(da, x, P[pre + "ln_1.weight"], mean1, rstd1, ws_ln, dx_res=dx1,
@@ -656,12 +656,12 @@ class _Engine:
         return dx0
 
     # -- the last block when only the pooled rows of its output are consumed -------------------------------------------
-    def _block_fwd_pooled(self, x, i: int, batch: int, layout, idx):
+    def _block_fwd_pooled(self, x, i: int, batch: int, L: int, layout, idx):
         """Attention as usual (every key/value is needed), then out_proj + residual, LayerNorm and the MLP on the `batch`
         pooled rows only.  Returns (x2 of the pooled rows [batch, width], saved)."""
         P, pre = self.P, f"transformer.resblocks.{i}."
         a, mean1, rstd1, a8 = self._ln_fwd(x, pre + "ln_1.weight", pre + "ln_1.bias")
-        max_len = layout.longest if layout is not None else self.seq
+        max_len = layout.longest if layout is not None else L
         pooled_ok = _POOLED_ATTN and ops.attention_pooled_supported(a.dtype, max_len, self.width // self.heads)
         if pooled_ok and self.pooled_split and self.weight_quant is None and self.act_quant is None:
             # Nobody reads the queries of the other rows either: the in_proj runs as k | v on every row and q on the pooled rows
@@ -671,7 +671,7 @@ class _Engine:
             a_s = ops.gather_rows(a, idx)
             kv = ops.linear_fwd(a, self.W(wn + "#kv"), bias[w:])
             q_s = ops.linear_fwd(a_s, self.W(wn + "#q"), bias[:w])
-            o_s, lse = ops.attention_pooled_fwd_split(q_s, kv, idx, batch, self.seq, self.heads, self.causal, layout)
+            o_s, lse = ops.attention_pooled_fwd_split(q_s, kv, idx, batch, L, self.heads, self.causal, layout)
             o_s.clipx_pooled_lse = lse
             qkv = (q_s, kv, a_s)
         else:
@@ -680,13 +680,13 @@ class _Engine:
             pass
         elif pooled_ok:
             # one query row per sequence: O(L d) instead of the whole L x L attention (the log-sum-exp rides on the output)
-            o_s, lse = ops.attention_pooled_fwd(qkv, idx, batch, self.seq, self.heads, self.causal, layout)
+            o_s, lse = ops.attention_pooled_fwd(qkv, idx, batch, L, self.heads, self.causal, layout)
             o_s.clipx_pooled_lse = lse
         else:
             if layout is not None:
                 o = ops.attention_packed_fwd(qkv, layout, self.heads, self.causal)
             else:
-                o = ops.attention_fwd(qkv, batch, self.seq, self.heads, self.causal)
+                o = ops.attention_fwd(qkv, batch, L, self.heads, self.causal)
             o_s = ops.gather_rows(o, idx)
         x_s = ops.gather_rows(x, idx)
         x1 = self._lin(o_s, pre + "attn.out_proj.weight", P[pre + "attn.out_proj.bias"], residual=x_s)
@@ -695,7 +695,7 @@ class _Engine:
         x2 = self._lin(h, pre + "mlp.c_proj.weight", P[pre + "mlp.c_proj.bias"], residual=x1)
         return x2, (x, a, mean1, rstd1, qkv, o_s, x1, c, mean2, rstd2, u, h)
 
-    def _block_bwd_pooled(self, dx2, saved, i: int, batch: int, prev_bias: Optional[str], layout, idx):
+    def _block_bwd_pooled(self, dx2, saved, i: int, batch: int, L: int, prev_bias: Optional[str], layout, idx):
         """Backward of _block_fwd_pooled.  dx2 [batch, width]: gradient of the pooled rows of the block output (the rest of
         that gradient is exactly zero).  Returns the dense gradient of the block input."""
         P, pre = self.P, f"transformer.resblocks.{i}."
@@ -729,7 +729,7 @@ class _Engine:
         if isinstance(qkv, tuple):
             q_s, kv, a_s = qkv
             w, wn = self.width, pre + "attn.in_proj_weight"
-            dq_s, dkv = ops.attention_pooled_bwd_split(q_s, kv, do_s, lse, idx, batch, self.seq, self.heads, self.causal, layout)
+            dq_s, dkv = ops.attention_pooled_bwd_split(q_s, kv, do_s, lse, idx, batch, L, self.heads, self.causal, layout)
             g, beta = self.G(wn)
             gb, beta_b = self.G(pre + "attn.in_proj_bias")
             ops.linear_wgrad(dkv, a, g[w:], beta, ws_wg, db=gb[w:], beta_b=beta_b)
@@ -744,13 +744,13 @@ class _Engine:
                 ops.colsum(dx1, gp, 1.0, ws_wg)
             return dx0
         if lse is not None:
-            dqkv = ops.attention_pooled_bwd(qkv, do_s, lse, idx, batch, self.seq, self.heads, self.causal, layout)
+            dqkv = ops.attention_pooled_bwd(qkv, do_s, lse, idx, batch, L, self.heads, self.causal, layout)
         else:
             do = ops.scatter_rows(do_s, idx, M)                    # zero except the pooled query rows
             if layout is not None:
                 dqkv = ops.attention_packed_bwd(qkv, do, layout, self.heads, self.causal)
             else:
-                dqkv = ops.attention_bwd(qkv, do, batch, self.seq, self.heads, self.causal)
+                dqkv = ops.attention_bwd(qkv, do, batch, L, self.heads, self.causal)
             del do
         g, beta = self.G(pre + "attn.in_proj_weight")
         gb, beta_b = self.G(pre + "attn.in_proj_bias")
@@ -782,14 +782,25 @@ class _Engine:
         P = self.P
         self._refresh_all()
         ckpt = self.tf.grad_checkpointing and save
+        L = self.seq
         if self.kind == "vision":
             batch = inp.shape[0]
             owner = self.owner
-            patches = ops.patchify(inp, owner.patch_size[0], owner.k_padded(self.dtype), self.dtype)
-            tok = ops.linear_fwd(patches, self._conv_w(), None)
-            x0 = ops.vision_assemble(tok, P["class_embedding"], P["positional_embedding"], batch, self.seq)
+            # patch dropout (reference transformer.py:712): while training, only the kept patches are embedded and every block
+            # runs on 1 + keep rows per image; the mask and L travel in ctx to the backward and the checkpoint recompute
+            pd = owner.patch_dropout
+            keep_idx = pd.draw(batch, self.seq - 1, inp.device) if (owner.training and pd.prob > 0) else None
+            if keep_idx is None:
+                patches = ops.patchify(inp, owner.patch_size[0], owner.k_padded(self.dtype), self.dtype)
+                tok = ops.linear_fwd(patches, self._conv_w(), None)
+                x0 = ops.vision_assemble(tok, P["class_embedding"], P["positional_embedding"], batch, self.seq)
+            else:
+                L = 1 + keep_idx.shape[1]
+                patches = ops.patchify_keep(inp, owner.patch_size[0], owner.k_padded(self.dtype), self.dtype, keep_idx)
+                tok = ops.linear_fwd(patches, self._conv_w(), None)
+                x0 = ops.vision_assemble_keep(tok, P["class_embedding"], P["positional_embedding"], keep_idx, self.seq - 1)
             x, mean0, rstd0 = ops.layernorm_fwd(x0, P["ln_pre.weight"], P["ln_pre.bias"])
-            head = (patches, x0, mean0, rstd0)
+            head = (patches, x0, mean0, rstd0, keep_idx)
         else:
             batch = inp.shape[0]
             hd = self.width // self.heads          # packed attention kernels: head dim 64 (bf16), 32 / 64 / 80 (fp32)
@@ -803,7 +814,7 @@ class _Engine:
         layout = head[1] if self.kind == "text" else None
         self.last_layout = layout
         if self.kind == "vision":
-            idx = ops.stride_index(batch, self.seq, x.device)
+            idx = ops.stride_index(batch, L, x.device)
         else:
             idx = layout.eot_rows if layout is not None else ops.eot_index(inp)
         pruned = self.prune_last and not want_tokens and self.layers > 0
@@ -816,9 +827,9 @@ class _Engine:
                 for i in range(self.layers):
                     x_in = x
                     if pruned and i == self.layers - 1:
-                        x, sv = self._block_fwd_pooled(x, i, batch, layout, idx)
+                        x, sv = self._block_fwd_pooled(x, i, batch, L, layout, idx)
                     else:
-                        x, sv = self._block_fwd(x, i, batch, layout)
+                        x, sv = self._block_fwd(x, i, batch, L, layout)
                     if save:
                         blocks.append(sv if i >= self.layers - keep else (x_in,))
                 break
@@ -843,7 +854,7 @@ class _Engine:
             tok_all = torch.empty((M + 1, self.width), dtype=x.dtype, device=x.device)
             tok_all[M].zero_()
             _, mean_all, rstd_all = ops.layernorm_fwd(x, P[ln + ".weight"], P[ln + ".bias"], out=tok_all[:M])
-        ctx = (batch, head, blocks, x, idx, pooled, meanp, rstdp, ckpt, mean_all, rstd_all, pruned) if save else None
+        ctx = (batch, head, blocks, x, idx, pooled, meanp, rstdp, ckpt, mean_all, rstd_all, pruned, L) if save else None
         if want_tokens:
             return feat, ctx, tok_all
         return feat, ctx
@@ -958,7 +969,7 @@ class _Engine:
 
     def _backward(self, ctx, dfeat: Optional[torch.Tensor], dtok_all: Optional[torch.Tensor] = None) -> List[Optional[torch.Tensor]]:
         P = self.P
-        batch, head, blocks, x_last, idx, pooled, meanp, rstdp, ckpt, mean_all, rstd_all, pruned = ctx
+        batch, head, blocks, x_last, idx, pooled, meanp, rstdp, ckpt, mean_all, rstd_all, pruned, L = ctx
         if dfeat is None:
             dfeat = torch.zeros((batch, self.embed_dim), dtype=torch.float32, device=x_last.device)
         dev = dfeat.device
@@ -1006,25 +1017,28 @@ class _Engine:
             sv = blocks[i]
             last_pruned = pruned and i == self.layers - 1
             if len(sv) == 1:          # a checkpointed block: only its input was kept
-                _, sv = (self._block_fwd_pooled(sv[0], i, batch, layout, idx) if last_pruned
-                         else self._block_fwd(sv[0], i, batch, layout, need_out=False))
+                _, sv = (self._block_fwd_pooled(sv[0], i, batch, L, layout, idx) if last_pruned
+                         else self._block_fwd(sv[0], i, batch, L, layout, need_out=False))
             prev_bias = f"transformer.resblocks.{i - 1}.mlp.c_proj.bias" if i > 0 else None
             if last_pruned:
-                dx = self._block_bwd_pooled(dx, sv, i, batch, prev_bias, layout, idx)
+                dx = self._block_bwd_pooled(dx, sv, i, batch, L, prev_bias, layout, idx)
             else:
-                dx = self._block_bwd(dx, sv, i, batch, prev_bias, layout)
+                dx = self._block_bwd(dx, sv, i, batch, L, prev_bias, layout)
             blocks[i] = None
             step = max(1, -(-self.layers // max(1, self.grad_chunks)))
             if i > 0 and (self.layers - i) % step == 0:
                 self._grads_ready(i)
         if self.kind == "vision":
-            patches, x0, mean0, rstd0 = head
+            patches, x0, mean0, rstd0, keep_idx = head
             dx0 = ops.layernorm_bwd(dx, x0, P["ln_pre.weight"], mean0, rstd0, ws_ln)
             self._ln_finish(ws_ln, self.width, "ln_pre.weight", "ln_pre.bias", None)
             gpos, bpos = self.G("positional_embedding")
             gcls, bcls = self.G("class_embedding")
             assert bpos == bcls
-            dtok = ops.vision_assemble_bwd(dx0, batch, self.seq, gpos, gcls, bpos)
+            if keep_idx is None:
+                dtok = ops.vision_assemble_bwd(dx0, batch, self.seq, gpos, gcls, bpos)
+            else:
+                dtok = ops.vision_assemble_keep_bwd(dx0, keep_idx, self.seq - 1, gpos, gcls, bpos)
             self.owner.conv_wgrad(self, dtok, patches)
         else:
             text, layout = head
@@ -1173,11 +1187,68 @@ def _to_2tuple(x):
     return tuple(x) if isinstance(x, (tuple, list)) else (x, x)
 
 
+class PatchDropout(nn.Module):
+    """Patch dropout (FLIP, arXiv 2212.00794; reference transformer.py:48-88 with exclude_first_token=True, as its
+    VisionTransformer builds it).  A control object without parameters or buffers (the state dict is unchanged): while the image
+    tower is in training mode and prob > 0, every forward draws which `num_keep(G2)` patch tokens of each image are kept, and the
+    tower's kernels run on those (the class token always stays); otherwise nothing of it runs.
+
+    rng="device" (default): one 63-bit key per forward from torch's default CPU generator (so masks follow the seed; no device
+    sync), expanded on the device by clipx_patch_keep_index: uniform without replacement, ascending.  The same distribution as
+    the reference's, not its random stream.
+    rng="torch": the reference's own draw, `torch.randn(batch, G2).topk(keep).indices` on the CPU, copied to the device
+    (parity / reproduction mode)."""
+
+    def __init__(self, prob: float = 0.5, exclude_first_token: bool = True, rng: str = "device"):
+        super().__init__()
+        if not (0 <= prob < 1.0):
+            raise ValueError(f"patch dropout probability must be in [0, 1), got {prob}")
+        if not exclude_first_token:
+            raise NotImplementedError("patch dropout without exclude_first_token is not supported (no config reaches it)")
+        self.prob = float(prob)
+        self.exclude_first_token = True
+        self.rng = rng
+        self._last_keep_index = None
+
+    @property
+    def rng(self) -> str:
+        return self._rng
+
+    @rng.setter
+    def rng(self, value: str):
+        if value not in ("device", "torch"):
+            raise ValueError(f"patch dropout rng must be 'device' or 'torch', got {value!r}")
+        self._rng = value
+
+    def num_keep(self, G2: int) -> int:
+        """reference transformer.py:76-77, in Python float: p = 0.9, G2 = 20 keeps 1"""
+        return max(1, int(G2 * (1 - self.prob)))
+
+    @property
+    def last_keep_index(self) -> Optional[torch.Tensor]:
+        """int32 [batch, keep] on the device: the mask of the last training-mode forward (None before the first)"""
+        return self._last_keep_index
+
+    def draw(self, batch: int, G2: int, device) -> torch.Tensor:
+        keep = self.num_keep(G2)
+        if self.rng == "torch":
+            # glue: the reference's CPU draw, byte for byte (transformer.py:79-80)
+            idx = torch.randn(batch, G2).topk(keep, dim=-1).indices.to(torch.int32).to(device)
+        else:
+            key = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
+            idx = ops.patch_keep_index(batch, G2, keep, key, device)
+        self._last_keep_index = idx
+        return idx
+
+    def extra_repr(self) -> str:
+        return f"prob={self.prob}, rng={self.rng!r}"
+
+
 class VisionTransformer(nn.Module):
     """Image tower (reference transformer.py:515-836, 'tok' pooling, learnable pos-embed)."""
 
     def __init__(self, image_size, patch_size: int, width: int, layers: int, heads: int, mlp_ratio: float,
-                 output_dim: int, act: int = ACT_GELU):
+                 output_dim: int, act: int = ACT_GELU, patch_dropout: float = 0.0):
         super().__init__()
         self.image_size = _to_2tuple(image_size)
         self.patch_size = _to_2tuple(patch_size)
@@ -1192,6 +1263,7 @@ class VisionTransformer(nn.Module):
         self.ln_pre = LayerNormParams(width)
         self.transformer = Transformer(width, layers, heads, mlp_ratio)
         self.ln_post = LayerNormParams(width)
+        self.patch_dropout = PatchDropout(patch_dropout)
         self._names = [n for n, _ in self.named_parameters()]
         seq = self.grid_size[0] * self.grid_size[1] + 1
         self._engine = _Engine("vision", self, self.transformer, seq, False, act, output_dim, self._names)
@@ -1261,14 +1333,12 @@ class CLIP(nn.Module):
                           ("no_causal_mask", text_cfg.no_causal_mask), ("ls_init_value", vision_cfg.ls_init_value)):
             if val:
                 raise NotImplementedError(f"{flag} is outside the MI355X hot path (plain ViT + text transformer CLIP)")
-        if vision_cfg.patch_dropout and vision_cfg.patch_dropout > 0:
-            raise NotImplementedError("patch_dropout is outside the MI355X hot path")
         self.output_dict = output_dict
         self.precision = precision
         act = ACT_QUICKGELU if quick_gelu else ACT_GELU
         self.visual = VisionTransformer(vision_cfg.image_size, vision_cfg.patch_size, vision_cfg.width,
                                         vision_cfg.layers, vision_cfg.width // vision_cfg.head_width,
-                                        vision_cfg.mlp_ratio, embed_dim, act)
+                                        vision_cfg.mlp_ratio, embed_dim, act, patch_dropout=vision_cfg.patch_dropout or 0.0)
         # text tower parameters live at top level (reference model.py:569-599)
         self.context_length = text_cfg.context_length
         self.vocab_size = text_cfg.vocab_size
@@ -1462,6 +1532,9 @@ class ColXLIP(CLIP):
                  init_logit_scale: float = math.log(1 / 0.07), init_logit_bias: Optional[float] = None,
                  cast_dtype: Optional[torch.dtype] = None, output_dict: bool = True, alpha: float = 0.5,
                  precision: str = "fp32"):
+        pd = vision_cfg.get("patch_dropout") if isinstance(vision_cfg, dict) else getattr(vision_cfg, "patch_dropout", 0.0)
+        if pd and pd > 0:
+            raise NotImplementedError("patch_dropout is not supported for ColXLIP: its token MaxSim path reads every patch token")
         super().__init__(embed_dim, vision_cfg, text_cfg, quick_gelu=quick_gelu, init_logit_scale=init_logit_scale,
                          init_logit_bias=init_logit_bias, cast_dtype=cast_dtype, output_dict=True, precision=precision)
         self.alpha = alpha

@@ -411,6 +411,51 @@ def vision_assemble_bwd(dx0, batch, tokens, dpos, dcls, beta):
 
 
 @family("embed")
+def patch_keep_index(batch, G2, keep, key, device):
+    """int32 [batch, keep]: `keep` distinct patch positions of [0, G2) per sample, uniform, ascending; a function of the
+    63-bit `key` and the sample index only (patch dropout's mask, drawn on the device)."""
+    idx = torch.empty((batch, keep), dtype=torch.int32, device=device)
+    check(_lib.lib().clipx_patch_keep_index(batch, G2, keep, int(key), _p(idx), _stream()))
+    return idx
+
+
+@family("embed")
+def patchify_keep(image, P, Kp, dtype, keep_idx):
+    """The rows of patchify(image, P, Kp, dtype) picked by keep_idx [b, keep]: [b*keep, Kp]."""
+    b, c, H, W = image.shape
+    assert c == 3 and keep_idx.dtype == torch.int32 and keep_idx.shape[0] == b
+    keep = keep_idx.shape[1]
+    out = torch.empty((b * keep, Kp), dtype=dtype, device=image.device)
+    check(_lib.lib().clipx_patchify_keep(dt_code(image.dtype), dt_code(dtype), b, H, W, P, Kp, keep, _p(_c(keep_idx)),
+                                         _p(_c(image)), _p(out), _stream()))
+    return out
+
+
+@family("embed")
+def vision_assemble_keep(tok, cls, pos, keep_idx, G2):
+    """x0 [b*(1+keep), width]: cls + pos[0], then tok[b*keep + j] + pos[1 + keep_idx[b, j]]."""
+    batch, keep = keep_idx.shape
+    width = tok.shape[-1]
+    x0 = torch.empty((batch * (keep + 1), width), dtype=tok.dtype, device=tok.device)
+    check(_lib.lib().clipx_vision_assemble_keep(dt_code(tok.dtype), batch, keep, G2, width, _p(_c(tok)), _p(cls), _p(pos),
+                                                _p(_c(keep_idx)), _p(x0), _stream()))
+    return x0
+
+
+@family("embed")
+def vision_assemble_keep_bwd(dx0, keep_idx, G2, dpos, dcls, beta):
+    """dtok [b*keep, width]; dpos / dcls = beta * themselves + the gradient scattered to the kept positions."""
+    batch, keep = keep_idx.shape
+    width = dx0.shape[-1]
+    dtok = torch.empty((batch * keep, width), dtype=dx0.dtype, device=dx0.device)
+    nbytes = int(_lib.lib().clipx_vision_assemble_keep_bwd_ws_bytes(G2, width))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dx0.device)
+    check(_lib.lib().clipx_vision_assemble_keep_bwd(dt_code(dx0.dtype), batch, keep, G2, width, _p(_c(dx0)), _p(_c(keep_idx)),
+                                                    _p(dtok), _p(dpos), _p(dcls), float(beta), _p(ws), nbytes, _stream()))
+    return dtok
+
+
+@family("embed")
 def text_embed(text, table, pos, dtype):
     b, L = text.shape
     vocab, width = table.shape

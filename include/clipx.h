@@ -158,6 +158,27 @@ int clipx_vision_assemble(int dtype, int batch, int tokens, int width, const voi
 size_t clipx_vision_assemble_bwd_ws_bytes(int tokens, int width);
 int clipx_vision_assemble_bwd(int dtype, int batch, int tokens, int width, const void* dx0,
                               void* dtok, float* dpos, float* dcls, float beta, float* ws, size_t ws_bytes, void* stream);
+/* ---- patch dropout (PatchDropout, transformer.py:48-88, applied before ln_pre at :712): while training, each image keeps
+ * `keep` = max(1, int(G2 * (1 - prob))) of its G2 patch tokens (:76-77); the tower runs on 1 + keep rows per image.
+ * keep_idx: int32 [batch, keep] of patch positions in [0, G2), distinct within a row; no kernel assumes it sorted.
+ * keep_index: the mask drawn on the device (replaces `torch.randn(batch, G2).topk(keep)`, :79-80): `keep` distinct positions
+ * per sample, uniform without replacement, ascending, a function of (key, sample) only.  G2 <= 1024.                        */
+int clipx_patch_keep_index(int batch, int G2, int keep, uint64_t key, int* keep_idx, void* stream);
+/* patches[b*keep + j, Kp] = row b*G2 + keep_idx[b, j] of clipx_patchify (the same bits): the patch-embed GEMM input of the
+ * kept patches only (conv1 as GEMM, transformer.py:702-704, followed by the gather x[batch_indices, patch_indices_keep] :82). */
+int clipx_patchify_keep(int img_dtype, int dtype, int batch, int H, int W, int P, int Kp, int keep,
+                        const int* keep_idx, const void* image, void* patches, void* stream);
+/* x0[b, 0] = cls + pos[0]; x0[b, 1+j] = tok[b*keep+j] + pos[1 + keep_idx[b, j]]  (transformer.py:707-712 with :82-85): the
+ * kept rows of clipx_vision_assemble, bit for bit.                                                                          */
+int clipx_vision_assemble_keep(int dtype, int batch, int keep, int G2, int width, const void* tok,
+                               const float* cls, const float* pos, const int* keep_idx, void* x0, void* stream);
+/* backward: dtok[b*keep+j] = dx0[b, 1+j]; dpos[0] = beta*dpos[0] + sum_b dx0[b, 0], dcls likewise;
+ * dpos[1+p] = beta*dpos[1+p] + sum over (b, j) with keep_idx[b, j] = p of dx0[b, 1+j] (beta*dpos exactly where no sample kept
+ * p).  Partial sums over batch parts added in a fixed order: the same result every run.
+ * ws: clipx_vision_assemble_keep_bwd_ws_bytes() bytes.                                                                       */
+size_t clipx_vision_assemble_keep_bwd_ws_bytes(int G2, int width);
+int clipx_vision_assemble_keep_bwd(int dtype, int batch, int keep, int G2, int width, const void* dx0, const int* keep_idx,
+                                   void* dtok, float* dpos, float* dcls, float beta, float* ws, size_t ws_bytes, void* stream);
 /* x0[b,l] = table[text[b,l]] + pos[l]   (transformer.py:980,988; text int64)             */
 int clipx_text_embed(int dtype, int batch, int L, int width, int vocab, const int64_t* text,
                      const float* table, const float* pos, void* x0, void* stream);
