@@ -2,7 +2,7 @@
 
 Only the plain-CLIP branch of `create_model` is on the MI355X hot path; branches that fetch
 from the network (hf-hub, OpenAI / pretrained tags), timm / HF towers, torchscript and the
-CoCa / SigLIP / distillation losses raise with a message saying so.
+CoCa loss raise with a message saying so.
 """
 import json
 import logging
@@ -17,7 +17,7 @@ from typing import Any, Dict, Optional, Tuple, Union
 import torch
 import torch.nn.functional as F
 
-from .loss import ClipLoss, ColClipLoss, SigLipLoss
+from .loss import ClipLoss, ColClipLoss, DistillClipLoss, SigLipLoss
 from .model import CLIP, ColXLIP, get_cast_dtype, set_model_preprocess_cfg
 
 HF_HUB_PREFIX = 'hf-hub:'
@@ -410,9 +410,15 @@ def create_model_and_transforms(
     return model, preprocess_train, preprocess_val
 
 
+def distill_enabled(args) -> bool:
+    """Distillation is on when both --distill-model and --distill-pretrained are given (open_clip's trainer)."""
+    return bool(getattr(args, "distill_model", None)) and bool(getattr(args, "distill_pretrained", None))
+
+
 def create_loss(args):
-    """Loss module for `args.model` (boundary: reference factory.py:424-461): SigLipLoss under --siglip, ColClipLoss for a
-    colxlip model (global + token-level MaxSim contrastive terms mixed by --alpha), ClipLoss otherwise."""
+    """Loss module for `args.model` (boundary: reference factory.py:424-461): SigLipLoss under --siglip, DistillClipLoss when
+    a teacher is given (--distill-model + --distill-pretrained), ColClipLoss for a colxlip model (global + token-level MaxSim
+    contrastive terms mixed by --alpha), ClipLoss otherwise."""
     family = args.model.lower()
     if "coca" in family:
         raise NotImplementedError("CoCaLoss is outside the MI355X hot path")
@@ -422,10 +428,14 @@ def create_loss(args):
         if "colxlip" in family:
             raise ValueError("--siglip needs a CLIP model: a ColXLIP model's output carries token features SigLipLoss cannot take")
         return SigLipLoss(rank=args.rank, world_size=args.world_size, dist_impl=getattr(args, "loss_dist_impl", None))
-    if getattr(args, "distill_model", None):
-        raise NotImplementedError("DistillClipLoss is outside the MI355X hot path")
     common = dict(local_loss=args.local_loss, gather_with_grad=args.gather_with_grad, cache_labels=True,
                   rank=args.rank, world_size=args.world_size, use_horovod=getattr(args, "horovod", False))
+    if distill_enabled(args):
+        # open_clip's trainer path (the reference parses --distill-model but its main.py:214 never builds a teacher)
+        if "colxlip" in family:
+            raise ValueError("distillation needs a CLIP student: a ColXLIP model's loss has token-level terms DistillClipLoss "
+                             "cannot take")
+        return DistillClipLoss(**common)
     if "colxlip" in family:
         return ColClipLoss(alpha=getattr(args, "alpha", 0.5), rows_local=bool(getattr(args, "colclip_rows_local", False)), **common)
     return ClipLoss(**common)

@@ -975,3 +975,171 @@ class SigLipLoss(nn.Module):
         else:
             loss = _SigmoidRing.apply(image_features, text_features, logit_scale, logit_bias, self.rank, W, self.dist_impl, want)
         return {"contrastive_loss": loss} if output_dict else loss
+
+
+# --------------------------------------------------------------------------- DistillClipLoss (reference loss.py:343-379)
+def _prep_scaled(a, scale):
+    a = a.contiguous().float()
+    scale = scale.detach().float().reshape(1).contiguous()
+    return a, scale, ops.scale_by_dev(a, scale)
+
+
+class _DistillCE(torch.autograd.Function):
+    """(contrastive, distill) of one problem: s = (scale*a) @ b.T (student), t = (tscale*ta) @ tb.T (teacher),
+    contrastive = w * sum_r CE(s[r,:], r + off), distill = w * sum_r -(softmax(t[r,:]) * log_softmax(s[r,:])).sum()
+    [+ the same over columns when symmetric], w = 0.5 / rows.
+
+    Neither logits matrix is ever written to memory (csrc/loss_distill.hip): the forward keeps per-tile statistics of both,
+    the backward recomputes both tiles per student operand.  The teacher gets no gradient here (distill_ce routes a teacher
+    that needs one to _DistillCEDense)."""
+
+    @staticmethod
+    def forward(ctx, a, b, scale, ta, tb, tscale, label_off: int, symmetric: bool):
+        with phase("loss.fwd"):
+            a, scale, a_s = _prep_scaled(a, scale)
+            b = b.contiguous().float()
+            _, tscale, ta_s = _prep_scaled(ta, tscale)
+            tb = tb.contiguous().float()
+            r = a.shape[0]
+            if symmetric:
+                assert r == b.shape[0] and label_off == 0
+            w = 0.5 / r
+            loss2 = torch.zeros((2,), dtype=torch.float32, device=a.device)
+            st_r, st_c = ops.distill_fused_fwd(a_s, b, ta_s, tb, label_off, symmetric, w, w, loss2)
+        ctx.save_for_backward(a_s, b, ta_s, tb, scale, st_r, st_c if st_c is not None else st_r)
+        ctx.label_off, ctx.symmetric, ctx.w = label_off, symmetric, w
+        return loss2[0].clone(), loss2[1].clone()
+
+    @staticmethod
+    def backward(ctx, gc, gd):
+        a_s, b, ta_s, tb, scale, st_r, st_c = ctx.saved_tensors
+        off, w = ctx.label_off, ctx.w
+        st_c = st_c if ctx.symmetric else None
+        with phase("loss.bwd"):
+            gc = gc.reshape(1).float().contiguous()
+            gd = gd.reshape(1).float().contiguous()
+            need_a, need_b, need_s = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+            da = db = ds = None
+            dscale = torch.zeros((1,), dtype=torch.float32, device=a_s.device) if need_s else None
+            if need_a or need_s:
+                # rows of `a` own the walk: d(a) = scale * ds @ b; d(scale) = sum ds*s / scale rides along
+                da = ops.distill_fused_bwd(a_s, b, ta_s, tb, st_r, w, off, st_c, w, 0, gc, gd, scale, dscale, scale)
+                if not need_a:
+                    da = None
+            if need_b:
+                # rows of `b` own the walk: d(b) = ds.T @ (scale*a), both tiles seen transposed
+                db = ops.distill_fused_bwd(b, a_s, tb, ta_s, st_c, w, 0, st_r, w, off, gc, gd, None)
+            if need_s:
+                ds = dscale.reshape(())
+        return da, db, ds, None, None, None, None, None
+
+
+class _DistillCEDense(torch.autograd.Function):
+    """The same two losses with both logits matrices in memory: embed dims the fused kernels are not instantiated for, and a
+    teacher whose features or scale need a gradient (dt = -w * g_d * pi * (s - sum pi s), reference autograd of loss.py:345)."""
+
+    @staticmethod
+    def forward(ctx, a, b, scale, ta, tb, tscale, label_off: int, symmetric: bool):
+        a, scale, a_s = _prep_scaled(a, scale)
+        b = b.contiguous().float()
+        _, tscale, ta_s = _prep_scaled(ta, tscale)
+        tb = tb.contiguous().float()
+        r, c = a.shape[0], b.shape[0]
+        if symmetric:
+            assert r == c and label_off == 0
+        s = torch.empty((r, c), dtype=torch.float32, device=a.device)
+        ops.gemm_f32(r, c, a.shape[1], a_s, a.shape[1], 1, b, 1, b.shape[1], s, c)
+        t = torch.empty((r, c), dtype=torch.float32, device=a.device)
+        ops.gemm_f32(r, c, ta.shape[1], ta_s, ta.shape[1], 1, tb, 1, tb.shape[1], t, c)
+        w = 0.5 / r
+        loss2 = torch.zeros((2,), dtype=torch.float32, device=a.device)
+        st_r, st_c = ops.distill_dense_fwd(s, t, label_off, symmetric, w, w, loss2)
+        ctx.save_for_backward(a_s, b, ta_s, tb, scale, tscale, s, t, st_r, st_c if st_c is not None else st_r)
+        ctx.label_off, ctx.symmetric, ctx.w = label_off, symmetric, w
+        return loss2[0].clone(), loss2[1].clone()
+
+    @staticmethod
+    def backward(ctx, gc, gd):
+        a_s, b, ta_s, tb, scale, tscale, s, t, st_r, st_c = ctx.saved_tensors
+        r, e = a_s.shape
+        c, et = b.shape[0], ta_s.shape[1]
+        gc = gc.reshape(1).float().contiguous()
+        gd = gd.reshape(1).float().contiguous()
+        want_t = any(ctx.needs_input_grad[3:6])
+        dscales = torch.zeros((2,), dtype=torch.float32, device=s.device)
+        # s -> ds and t -> dt in place (consumes the saved logits)
+        ops.distill_dense_grad(s, t, ctx.label_off, st_r, ctx.w, st_c if ctx.symmetric else None, ctx.w, gc, gd, want_t,
+                               scale, tscale if want_t else None, dscales)
+        da = db = dta = dtb = None
+        if ctx.needs_input_grad[0]:
+            tmp = torch.empty((r, e), dtype=torch.float32, device=s.device)
+            ops.gemm_f32(r, e, c, s, c, 1, b, e, 1, tmp, e)                 # ds @ b
+            da = ops.scale_by_dev(tmp, scale, out=tmp)
+        if ctx.needs_input_grad[1]:
+            db = torch.empty((c, e), dtype=torch.float32, device=s.device)
+            ops.gemm_f32(c, e, r, s, 1, c, a_s, e, 1, db, e)                # ds.T @ (scale*a)
+        if ctx.needs_input_grad[3]:
+            tmp = torch.empty((r, et), dtype=torch.float32, device=s.device)
+            ops.gemm_f32(r, et, c, t, c, 1, tb, et, 1, tmp, et)             # dt @ tb
+            dta = ops.scale_by_dev(tmp, tscale, out=tmp)
+        if ctx.needs_input_grad[4]:
+            dtb = torch.empty((c, et), dtype=torch.float32, device=s.device)
+            ops.gemm_f32(c, et, r, t, 1, c, ta_s, et, 1, dtb, et)          # dt.T @ (tscale*ta)
+        ds = dscales[0].reshape(()) if ctx.needs_input_grad[2] else None
+        dts = dscales[1].reshape(()) if ctx.needs_input_grad[5] else None
+        return da, db, ds, dta, dtb, dts, None, None
+
+
+def distill_ce(a, b, scale, ta, tb, tscale, label_off: int, symmetric: bool):
+    """(contrastive, distill) of one problem; the fused kernels unless an embed dim is outside ops.FUSED_CE_DIMS or the
+    teacher needs a gradient."""
+    teacher_grad = torch.is_grad_enabled() and any(x.requires_grad for x in (ta, tb, tscale))
+    if not teacher_grad and a.shape[1] in ops.FUSED_CE_DIMS and ta.shape[1] in ops.FUSED_CE_DIMS:
+        return _DistillCE.apply(a, b, scale, ta, tb, tscale, label_off, symmetric)
+    return _DistillCEDense.apply(a, b, scale, ta, tb, tscale, label_off, symmetric)
+
+
+class DistillClipLoss(ClipLoss):
+    """reference loss.py:343-379: ClipLoss's contrastive term plus the cross-entropy of the student's logits against the
+    teacher's softmax, in both directions.  One fused launch pair per problem yields both losses (csrc/loss_distill.hip); the
+    teacher features are gathered like the student's (ClipLoss.get_logits gathers both pairs in the reference)."""
+
+    def dist_loss(self, teacher_logits, student_logits):
+        """reference loss.py:345 on materialised logits (API surface; forward never forms them)."""
+        return -(teacher_logits.softmax(dim=1) * student_logits.log_softmax(dim=1)).sum(dim=1).mean(dim=0)
+
+    def forward(
+            self,
+            image_features,
+            text_features,
+            logit_scale,
+            dist_image_features,
+            dist_text_features,
+            dist_logit_scale,
+            output_dict=False,
+            **kwargs,
+    ):
+        # NB like the reference (loss.py:347-376) logit_bias is not applied.
+        if not torch.is_tensor(dist_logit_scale):
+            dist_logit_scale = torch.tensor(float(dist_logit_scale), device=logit_scale.device)
+        if self.world_size > 1:
+            all_image_features, all_text_features = self._gather(image_features, text_features)
+            dist_all_image, dist_all_text = self._gather(dist_image_features, dist_text_features)
+            if self.local_loss:
+                off = image_features.shape[0] * self.rank
+                c_i, d_i = distill_ce(image_features, all_text_features, logit_scale, dist_image_features, dist_all_text,
+                                      dist_logit_scale, off, False)
+                c_t, d_t = distill_ce(text_features, all_image_features, logit_scale, dist_text_features, dist_all_image,
+                                      dist_logit_scale, off, False)
+                contrastive_loss, distill_loss = c_i + c_t, d_i + d_t
+            else:
+                contrastive_loss, distill_loss = distill_ce(all_image_features, all_text_features, logit_scale, dist_all_image,
+                                                            dist_all_text, dist_logit_scale, 0, True)
+        else:
+            contrastive_loss, distill_loss = distill_ce(image_features, text_features, logit_scale, dist_image_features,
+                                                        dist_text_features, dist_logit_scale, 0, True)
+
+        if output_dict:
+            return {"contrastive_loss": contrastive_loss, "distill_loss": distill_loss}
+
+        return contrastive_loss, distill_loss

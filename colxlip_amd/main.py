@@ -23,7 +23,7 @@ import torch
 
 from .data import get_data
 from .distributed import GradSync, broadcast_object, init_distributed_device, is_master
-from .factory import create_loss, create_model_and_transforms
+from .factory import create_loss, create_model, create_model_and_transforms, distill_enabled, get_model_config
 from .optim import FusedAdamW, ShardedAdamW, param_groups
 from .params import parse_args, unsupported_flag_values
 from . import scheduler as schedules
@@ -50,12 +50,51 @@ def get_latest_checkpoint(path: str):
     return max(found, key=_checkpoint_order) if found else None
 
 
+def distill_refusal(args):
+    """Why `main` cannot distil with these flags, or None.  EXTENSION: the reference parses --distill-model /
+    --distill-pretrained but its main.py:214 hard-wires `dist_model = None`; here they build a teacher the way open_clip's
+    trainer does.  Every check reads only the flags and the model configs (no device)."""
+    model, pretrained = getattr(args, "distill_model", None), getattr(args, "distill_pretrained", None)
+    if not model and not pretrained:
+        return None
+    if not (model and pretrained):
+        return "distillation needs both --distill-model and --distill-pretrained"
+    if int(getattr(args, "accum_freq", 1)) > 1:
+        return "distillation does not support --accum-freq > 1"
+    if getattr(args, "siglip", False):
+        return "distillation does not support --siglip"
+    for role, name in (("student", args.model), ("teacher", model)):
+        if "colxlip" in name.lower():
+            return f"distillation needs CLIP models: the {role} {name} is a ColXLIP model"
+        if "coca" in name.lower():
+            return f"distillation does not support CoCa models (the {role} is {name})"
+    s_cfg, t_cfg = get_model_config(args.model.replace("/", "-")), get_model_config(model.replace("/", "-"))
+    if t_cfg is None:
+        return f"teacher model {model} not found"
+    if s_cfg is None:
+        return None                 # create_model reports an unknown student itself
+
+    def size(cfg, forced=None):
+        v = forced or cfg["vision_cfg"]["image_size"]
+        v = v[0] if isinstance(v, (list, tuple)) and len(v) == 1 else v
+        return tuple(v) if isinstance(v, (list, tuple)) else (v, v)
+
+    forced = getattr(args, "force_image_size", None)
+    for what, sv, tv in (("image size", size(s_cfg, forced), size(t_cfg)),
+                         ("context length", s_cfg["text_cfg"].get("context_length", 77), t_cfg["text_cfg"].get("context_length", 77)),
+                         ("vocabulary size", s_cfg["text_cfg"].get("vocab_size", 49408), t_cfg["text_cfg"].get("vocab_size", 49408))):
+        if sv != tv:
+            return f"the teacher sees the student's batch: its {what} {tv} differs from the student's {sv}"
+    return None
+
+
 class _Run:
     def __init__(self, argv):
         self.args = parse_args(argv)
         self.device = init_distributed_device(self.args)
         self.master = is_master(self.args)
         self.model = self.core = self.grad_sync = self.optimizer = self.scheduler = None
+        self.dist_model = None
         self.data, self.start_epoch, self.writer = {}, 0, None
 
     # ---- experiment directory, logging, resume target ------------------------------------------------------------
@@ -66,6 +105,10 @@ class _Run:
         bad = unsupported_flag_values(a)
         if bad:
             logging.error("flags outside this stack: " + ", ".join(f"--{k.replace('_', '-')}={v!r}" for k, v in bad))
+            return False
+        why = distill_refusal(a)
+        if why:
+            logging.error(why)
             return False
         if a.name is None:
             stamp = broadcast_object(a, datetime.now().strftime("%Y_%m_%d-%H_%M_%S"))
@@ -133,6 +176,10 @@ class _Run:
             image_mean=a.image_mean, image_std=a.image_std, image_interpolation=a.image_interpolation,
             image_resize_mode=a.image_resize_mode, aug_cfg=a.aug_cfg, pretrained_image=a.pretrained_image, output_dict=True,
             **siglip_init)
+        if distill_enabled(a):
+            # the teacher: no DDP wrap, not in the optimizer, not checkpointed; it runs without a graph (train_one_epoch)
+            self.dist_model = create_model(a.distill_model, a.distill_pretrained, device=self.device, precision=a.precision,
+                                           output_dict=True)
         random_seed(a.seed, a.rank)
         if a.grad_checkpointing:
             self.core.set_grad_checkpointing()
@@ -208,7 +255,7 @@ class _Run:
         for epoch in range(self.start_epoch, a.epochs):
             if self.master:
                 logging.info(f'Start epoch {epoch}')
-            train_one_epoch(self.model, self.data, loss, epoch, self.optimizer, None, self.scheduler, None, a,
+            train_one_epoch(self.model, self.data, loss, epoch, self.optimizer, None, self.scheduler, self.dist_model, a,
                             tb_writer=self.writer, grad_sync=self.grad_sync)
             if has_eval:
                 evaluate(self.model, self.data, epoch + 1, a, tb_writer=self.writer)

@@ -677,6 +677,68 @@ def sigmoid_dense(z, scale_dev, bias_dev, pos_off, inv_r):
     return out3
 
 
+@family("loss")
+def distill_fused_fwd(P, Q, TP, TQ, label_off, symmetric, w_own, w_oth, loss2):
+    """Row (and, symmetric, column) statistics (lse_s, lse_t, X) of s = P @ Q.T and t = TP @ TQ.T without either in memory;
+    loss2 += [contrastive, distill].  Returns (stats_own [3, np], stats_oth [3, nq] or None)."""
+    np_, Es = P.shape
+    nq, Et = Q.shape[0], TP.shape[1]
+    assert Q.shape[1] == Es and TP.shape[0] == np_ and TQ.shape == (nq, Et)
+    L = _lib.lib()
+    nbytes = int(L.clipx_distill_fused_ws_bytes(np_, nq, int(symmetric)))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=P.device)
+    st_own = torch.empty((3, np_), dtype=torch.float32, device=P.device)
+    st_oth = torch.empty((3, nq), dtype=torch.float32, device=P.device) if symmetric else None
+    check(L.clipx_distill_fused_fwd(np_, nq, Es, Et, _p(_c(P)), _p(_c(Q)), _p(_c(TP)), _p(_c(TQ)), int(label_off),
+                                    int(symmetric), float(w_own), float(w_oth), _p(st_own), _p(st_oth), _p(loss2), _p(ws),
+                                    nbytes, _stream()))
+    return st_own, st_oth
+
+
+@family("loss")
+def distill_fused_bwd(P, Q, TP, TQ, st_own, w_own, off_own, st_oth, w_oth, off_oth, gc_dev, gd_dev, out_scale_dev,
+                      dscale_acc=None, scale_dev=None):
+    """dP = osc * ds @ Q with ds recomputed tile by tile (both upstream gradients folded in)."""
+    np_, Es = P.shape
+    nq, Et = Q.shape[0], TP.shape[1]
+    dP = torch.empty((np_, Es), dtype=torch.float32, device=P.device)
+    L = _lib.lib()
+    nbytes = int(L.clipx_distill_fused_bwd_ws_bytes(np_, nq, Es))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=P.device)
+    check(L.clipx_distill_fused_bwd(np_, nq, Es, Et, _p(_c(P)), _p(_c(Q)), _p(_c(TP)), _p(_c(TQ)), _p(st_own), float(w_own),
+                                    int(off_own), _p(st_oth), float(w_oth), int(off_oth), _p(gc_dev), _p(gd_dev),
+                                    _p(out_scale_dev), _p(dP), _p(dscale_acc), _p(scale_dev), _p(ws), nbytes, _stream()))
+    return dP
+
+
+@family("loss")
+def distill_dense_fwd(s, t, label_off, symmetric, w_row, w_col, loss2):
+    """Statistics and losses of materialised student / teacher logits [rows, cols]; returns (stats_row, stats_col or None)."""
+    rows, cols = s.shape
+    assert t.shape == s.shape
+    L = _lib.lib()
+    nbytes = int(L.clipx_distill_dense_ws_bytes(rows, cols))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=s.device)
+    st_row = torch.empty((3, rows), dtype=torch.float32, device=s.device)
+    st_col = torch.empty((3, cols), dtype=torch.float32, device=s.device) if symmetric else None
+    check(L.clipx_distill_dense_fwd(rows, cols, _p(s), s.stride(0), _p(t), t.stride(0), int(label_off), int(symmetric),
+                                    float(w_row), float(w_col), _p(st_row), _p(st_col), _p(loss2), _p(ws), nbytes, _stream()))
+    return st_row, st_col
+
+
+@family("loss")
+def distill_dense_grad(s, t, label_off, st_row, w_row, st_col, w_col, gc_dev, gd_dev, want_dt, scale_dev, tscale_dev,
+                       dscales2):
+    """In place s -> ds and (want_dt) t -> dt; dscales2 += [d(scale), d(teacher scale)]."""
+    rows, cols = s.shape
+    L = _lib.lib()
+    nbytes = int(L.clipx_distill_dense_ws_bytes(rows, cols))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=s.device)
+    check(L.clipx_distill_dense_grad(rows, cols, _p(s), s.stride(0), _p(t), t.stride(0), int(label_off), _p(st_row),
+                                     float(w_row), _p(st_col), float(w_col), _p(gc_dev), _p(gd_dev), int(want_dt),
+                                     _p(scale_dev), _p(tscale_dev), _p(dscales2), _p(ws), nbytes, _stream()))
+
+
 def scale_by_dev(x, s_dev, out=None):
     out = torch.empty_like(x) if out is None else out
     check(_lib.lib().clipx_scale_by_dev(x.numel(), _p(_c(x)), _p(s_dev), _p(out), _stream()))

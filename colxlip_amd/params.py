@@ -145,7 +145,7 @@ _FLAGS = {
 _INERT_ONLY = {
     "remote_sync": None, "copy_codebase": False, "huggingface_model_name": "", "use_bnb_linear": None,
     "horovod": False, "torchscript": False, "trace": False, "lock_image": False, "lock_text": False,
-    "distill_model": None, "distill_pretrained": None, "inference_with_flair": False,
+    "inference_with_flair": False,
     "imagenet_val": None, "imagenet_v2": None, "use_bn_sync": False, "dataset_resampled": False,
     "torchcompile": False,        # no tracing compiler in this stack (hand-written kernels behind autograd Functions)
 }

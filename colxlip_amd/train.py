@@ -49,7 +49,8 @@ def unwrap_model(model):
 
 def _with_total(losses):
     """The loss dict's sum is its total when it names none, as in open_clip's trainer: SigLipLoss returns only
-    `contrastive_loss` (reference loss.py:604), while the loop reads `total_loss` (reference train.py:135)."""
+    `contrastive_loss` (reference loss.py:604), DistillClipLoss `contrastive_loss` and `distill_loss` (loss.py:375), while
+    the loop reads `total_loss` (reference train.py:135)."""
     if "total_loss" not in losses:
         losses["total_loss"] = sum(losses.values())
     return losses
@@ -62,8 +63,9 @@ def backward(total_loss, scaler=None):
 class _StepRunner:
     """Everything between 'a full group of micro-batches is on the device' and 'the weights have moved'."""
 
-    def __init__(self, model, loss, optimizer, scaler, args, grad_sync):
+    def __init__(self, model, loss, optimizer, scaler, args, grad_sync, dist_model=None):
         self.model, self.loss, self.optimizer, self.scaler, self.args, self.grad_sync = model, loss, optimizer, scaler, args, grad_sync
+        self.dist_model = dist_model
         self.clip = getattr(args, "grad_clip_norm", None)
 
     def _no_sync(self):
@@ -76,7 +78,15 @@ class _StepRunner:
         return contextlib.nullcontext()
 
     def _single(self, images, texts):
+        dist_out = None
+        if self.dist_model is not None:
+            # the teacher (open_clip trainer semantics): no graph, so the towers keep no activations; its outputs enter the
+            # loss as dist_image_features / dist_text_features / dist_logit_scale
+            with torch.no_grad():
+                dist_out = self.dist_model(images, texts)
         out = self.model(images, texts)
+        if dist_out is not None:
+            out.update({f"dist_{k}": v for k, v in dist_out.items()})
         logit_scale = out["logit_scale"]
         losses = _with_total(self.loss(**out, output_dict=True))
         backward(losses["total_loss"], self.scaler)
@@ -145,18 +155,19 @@ class _null:
 
 def train_one_epoch(model, data, loss, epoch, optimizer, scaler, scheduler, dist_model, args, tb_writer=None,
                     grad_sync=None):
-    if dist_model is not None:
-        raise NotImplementedError("distillation (--distill) is outside the MI355X hot path")
     device = torch.device(args.device)
     input_dtype = get_input_dtype(args.precision)
     accum = max(1, int(args.accum_freq))
     model.train()
+    if dist_model is not None:
+        assert accum == 1, "distillation does not support --accum-freq > 1"
+        dist_model.eval()
     info = data["train"]
     info.set_epoch(epoch)
     loader = info.dataloader
     steps_per_epoch = loader.num_batches // accum
     digits = math.ceil(math.log(loader.num_samples + 1, 10))
-    run_step = _StepRunner(model, loss, optimizer, scaler, args, grad_sync)
+    run_step = _StepRunner(model, loss, optimizer, scaler, args, grad_sync, dist_model)
 
     def logs_at(step_in_epoch):
         return step_in_epoch % args.log_every_n_steps == 0 or step_in_epoch + 1 == steps_per_epoch

@@ -283,6 +283,41 @@ int clipx_sigmoid_fused_bwd(int r, int c, int E, const float* A, const float* B,
 size_t clipx_sigmoid_dense_ws_bytes(int rows, int cols);
 int clipx_sigmoid_dense(int rows, int cols, float* z, long ldz, const float* scale_dev, const float* bias_dev,
                         int pos_off, float inv_r, float* out3, void* ws, size_t ws_bytes, void* stream);
+/* ---- DistillClipLoss (loss.py:343-379): contrastive + distillation cross-entropy WITHOUT a logits matrix in memory
+ * (exact-fp32 MFMA tiles).  Student s[p,q] = P[p].Q[q] (P = logit_scale * own features [np,Es], Q [nq,Es]); teacher
+ * t[p,q] = TP[p].TQ[q] (TP = dist_logit_scale * own teacher features [np,Et], TQ [nq,Et]).
+ * fused_fwd (loss.py:343-345,359-373): per row stats_own[3][np] = (lse_s, lse_t, X = sum_q softmax(t)*s);
+ *   loss2[0] += w_own * sum_p (lse_s - s[p, p+label_off]),  loss2[1] += w_own * sum_p (lse_s - X);
+ *   symmetric (np == nq, label_off == 0) also the same over columns into stats_oth[3][nq] with w_oth.
+ *   ws: clipx_distill_fused_ws_bytes() bytes (per-tile partials: O(np*nq/64)).                                            */
+size_t clipx_distill_fused_ws_bytes(int np, int nq, int symmetric);
+int clipx_distill_fused_fwd(int np, int nq, int Es, int Et, const float* P, const float* Q, const float* TP, const float* TQ,
+                            int label_off, int symmetric, float w_own, float w_oth, float* stats_own, float* stats_oth,
+                            float* loss2, void* ws, size_t ws_bytes, void* stream);
+/* fused_bwd (loss.py:343-379) of one student operand, both tiles recomputed:  dP[p,:] = osc * sum_q ds(p,q) * Q[q,:],
+ *   ds = w_own*(g_c*(sigma_own - [q == p+off_own]) + g_d*(sigma_own - pi_own))
+ *      + w_oth*(g_c*(sigma_oth - [p == q+off_oth]) + g_d*(sigma_oth - pi_oth)),
+ *   sigma / pi: student / teacher softmax from the stats of fused_fwd (a NULL stats pointer drops its term);
+ *   g_c = *gc_dev, g_d = *gd_dev (the upstream gradients of the two losses); osc = *out_scale_dev (NULL: 1);
+ *   dscale_acc (optional) += sum ds*s / *scale_dev.  ws: clipx_distill_fused_bwd_ws_bytes() bytes.
+ *   Es, Et in {16,32,64,128,256,512,640,768,1024}.                                                                          */
+size_t clipx_distill_fused_bwd_ws_bytes(int np, int nq, int Es);
+int clipx_distill_fused_bwd(int np, int nq, int Es, int Et, const float* P, const float* Q, const float* TP, const float* TQ,
+                            const float* stats_own, float w_own, int off_own, const float* stats_oth, float w_oth,
+                            int off_oth, const float* gc_dev, const float* gd_dev, const float* out_scale_dev, float* dP,
+                            float* dscale_acc, const float* scale_dev, void* ws, size_t ws_bytes, void* stream);
+/* the same on materialised logits s, t [rows, cols] (any embed dims; loss.py:343-379).  dense_fwd: stats and loss2 as
+ *   fused_fwd (the rows always, the columns when symmetric).  dense_grad: in place s -> ds and (want_dt) t -> dt,
+ *   dt = -sum_dir w * g_d * pi * (s - X);  dscales2 (optional) += [sum ds*s / *scale_dev, sum dt*t / *tscale_dev]
+ *   (a NULL tscale_dev leaves dscales2[1]).  ws: clipx_distill_dense_ws_bytes() bytes.                                     */
+size_t clipx_distill_dense_ws_bytes(int rows, int cols);
+int clipx_distill_dense_fwd(int rows, int cols, const float* s, long lds, const float* t, long ldt, int label_off,
+                            int symmetric, float w_row, float w_col, float* stats_row, float* stats_col, float* loss2,
+                            void* ws, size_t ws_bytes, void* stream);
+int clipx_distill_dense_grad(int rows, int cols, float* s, long lds, float* t, long ldt, int label_off,
+                             const float* stats_row, float w_row, const float* stats_col, float w_col, const float* gc_dev,
+                             const float* gd_dev, int want_dt, const float* scale_dev, const float* tscale_dev,
+                             float* dscales2, void* ws, size_t ws_bytes, void* stream);
 /* out[i] = x[i] * (*s_dev): `logit_scale * image_features` with the scale left on the device
  * (loss.py:145-152 multiplies the features first, then takes the matmul).                    */
 int clipx_scale_by_dev(size_t n, const float* x, const float* s_dev, float* out, void* stream);
