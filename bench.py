@@ -6,12 +6,14 @@ at GLOBAL batch 4096 (BASELINE.json), bf16 operands / fp32 accumulate, synthetic
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
-  roofline     — the dominant kernel (bf16 MFMA NT GEMM: every forward linear and every dgrad),
-                 algorithmic FLOPs of its launches / their measured durations (HIP events recorded on the
-                 launch stream around each launch, in an instrumented step after the timed region).
-  cpu_baseline — the CPU oracle (a port of the reference's PyTorch path) timed on the host cores on a
-                 bounded sample (ViT-B/32, batch 32, fp32 full train steps), rank 0 at N=1 only.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps, writes
+--dump-outputs if asked and prints that line: nothing else.  --full adds, after the timed region, what needs runs of its own:
+  dense_text_rows — a short second measurement of the same step with all 77 text positions computed (--no-dense-compare: off).
+  roofline        — the dominant kernel (bf16 MFMA NT GEMM: every forward linear and every dgrad),
+                    algorithmic FLOPs of its launches / their measured durations (HIP events recorded on the
+                    launch stream around each launch, in an instrumented step after the timed region).
+  cpu_baseline    — the CPU oracle (a port of the reference's PyTorch path) timed on the host cores on a
+                    bounded sample (ViT-B/32, batch 32, fp32 full train steps), rank 0 at N=1 only (--no-cpu-baseline: off).
 
 --dump-outputs DIR writes what the last timed step computed on rank 0 as DIR/<name>.npy (float32): `loss`, every tensor of the
 model's output dict, and `param.<name>` / `grad.<name>` for every parameter after the optimizer step.  Inputs and init are seeded,
@@ -50,15 +52,18 @@ def parse():
     p.add_argument("--global-batch", type=int, default=4096)
     p.add_argument("--precision", default="bf16")
     p.add_argument("--grad-checkpointing", action="store_true")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--cpu-steps", type=int, default=15)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed region also measure the dense text layout, run the instrumented step behind `roofline` "
+                        "and time the CPU baseline (a plain run does only what `value` and --dump-outputs need)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--cpu-steps", type=int, default=15, help="with --full: timed CPU baseline steps at most")
     p.add_argument("--serial-towers", action="store_true",
                    help="run the two towers on one stream (per-kernel durations in a rocprofv3 trace are only meaningful "
                         "when kernels do not overlap; the default overlaps them and is what `value` reports)")
     p.add_argument("--dense-text", action="store_true",
                    help="compute all 77 text positions like the reference (default: only positions 0..EOT, packed rows)")
     p.add_argument("--no-dense-compare", action="store_true",
-                   help="skip the short second measurement with the dense text layout that is reported beside `value`")
+                   help="with --full: skip the short second measurement with the dense text layout that is reported beside `value`")
     p.add_argument("--force-dist", action="store_true",
                    help="1-GPU rehearsal of the multi-GPU path: RCCL process group of one rank, gradient all-reduce on")
     p.add_argument("--shard-optimizer", action="store_true",
@@ -413,7 +418,7 @@ def main():
 
     # ---- the same step with the reference's dense text layout (all 77 positions), a short second measurement
     dense = None
-    if layout is not None and not args.no_dense_compare:
+    if args.full and layout is not None and not args.no_dense_compare:
         model._text_engine.packed = False
         for _ in range(2):
             step()
@@ -432,40 +437,41 @@ def main():
         model._text_engine.packed = True
         step()
 
-    # ---- instrumented step: per-launch durations of the dominant kernel (bf16 NT GEMM).  The towers run on ONE
-    # stream here: with the default two streams a launch's begin-to-end time includes CUs held by the other tower's
-    # kernel, which says nothing about the kernel itself.
-    prev_streams = os.environ.get("CLIPX_TOWER_STREAMS")
-    os.environ["CLIPX_TOWER_STREAMS"] = "0"
-    if prev_streams != "0":
-        # activations now come from the main stream's allocator pool: release the side streams' cached blocks and
-        # run one untimed step so that no hipMalloc sits between an event and its launch
-        torch.cuda.synchronize()
-        torch.cuda.empty_cache()
+    if args.full:
+        # ---- instrumented step: per-launch durations of the dominant kernel (bf16 NT GEMM).  The towers run on ONE
+        # stream here: with the default two streams a launch's begin-to-end time includes CUs held by the other tower's
+        # kernel, which says nothing about the kernel itself.
+        prev_streams = os.environ.get("CLIPX_TOWER_STREAMS")
+        os.environ["CLIPX_TOWER_STREAMS"] = "0"
+        if prev_streams != "0":
+            # activations now come from the main stream's allocator pool: release the side streams' cached blocks and
+            # run one untimed step so that no hipMalloc sits between an event and its launch
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            step()
+            torch.cuda.synchronize()
+        timer = LaunchTimer()
+        import colxlip_amd.model as M
+        orig_f, orig_d = ops.linear_fwd, ops.linear_dgrad
+        ops.linear_fwd = timer.wrap(orig_f, lambda x, w, *a, **k: 2.0 * x.shape[0] * x.shape[1] * w.shape[0], _fwd_bytes)
+        ops.linear_dgrad = timer.wrap(orig_d, lambda dy, w, wt, *a, **k: 2.0 * dy.shape[0] * dy.shape[1] * (w.shape[1] if w is not None else wt.shape[0]), _dgrad_bytes)
+        # precision fp8_mfma: the forward linears and dgrads of the residual blocks run on gemm_fp8_nt8p_kernel -- in that mode IT is
+        # the dominant kernel, timed by itself and priced against the fp8 peak (the bf16 launches that remain -- patch embed,
+        # projections, the pooled last block -- are reported beside it)
+        timer8 = LaunchTimer()
+        orig_f8, orig_d8 = ops.linear_fwd_fp8, ops.linear_dgrad_fp8
+        ops.linear_fwd_fp8 = timer8.wrap(orig_f8, lambda x8, xe, w8, *a, **k: 2.0 * x8.shape[0] * x8.shape[1] * w8.shape[0], _fwd8_bytes)
+        ops.linear_dgrad_fp8 = timer8.wrap(orig_d8, lambda d8, de, wt8, *a, **k: 2.0 * d8.shape[0] * d8.shape[1] * wt8.shape[0], _dgrad8_bytes)
         step()
-        torch.cuda.synchronize()
-    timer = LaunchTimer()
-    import colxlip_amd.model as M
-    orig_f, orig_d = ops.linear_fwd, ops.linear_dgrad
-    ops.linear_fwd = timer.wrap(orig_f, lambda x, w, *a, **k: 2.0 * x.shape[0] * x.shape[1] * w.shape[0], _fwd_bytes)
-    ops.linear_dgrad = timer.wrap(orig_d, lambda dy, w, wt, *a, **k: 2.0 * dy.shape[0] * dy.shape[1] * (w.shape[1] if w is not None else wt.shape[0]), _dgrad_bytes)
-    # precision fp8_mfma: the forward linears and dgrads of the residual blocks run on gemm_fp8_nt8p_kernel -- in that mode IT is
-    # the dominant kernel, timed by itself and priced against the fp8 peak (the bf16 launches that remain -- patch embed,
-    # projections, the pooled last block -- are reported beside it)
-    timer8 = LaunchTimer()
-    orig_f8, orig_d8 = ops.linear_fwd_fp8, ops.linear_dgrad_fp8
-    ops.linear_fwd_fp8 = timer8.wrap(orig_f8, lambda x8, xe, w8, *a, **k: 2.0 * x8.shape[0] * x8.shape[1] * w8.shape[0], _fwd8_bytes)
-    ops.linear_dgrad_fp8 = timer8.wrap(orig_d8, lambda d8, de, wt8, *a, **k: 2.0 * d8.shape[0] * d8.shape[1] * wt8.shape[0], _dgrad8_bytes)
-    step()
-    n_launch, gemm_ms, gemm_flops, gemm_bytes = timer.totals()
-    n8, ms8, flops8, bytes8 = timer8.totals()
-    ops.linear_fwd, ops.linear_dgrad = orig_f, orig_d
-    ops.linear_fwd_fp8, ops.linear_dgrad_fp8 = orig_f8, orig_d8
-    if prev_streams is None:
-        del os.environ["CLIPX_TOWER_STREAMS"]
-    else:
-        os.environ["CLIPX_TOWER_STREAMS"] = prev_streams
-    achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+        n_launch, gemm_ms, gemm_flops, gemm_bytes = timer.totals()
+        n8, ms8, flops8, bytes8 = timer8.totals()
+        ops.linear_fwd, ops.linear_dgrad = orig_f, orig_d
+        ops.linear_fwd_fp8, ops.linear_dgrad_fp8 = orig_f8, orig_d8
+        if prev_streams is None:
+            del os.environ["CLIPX_TOWER_STREAMS"]
+        else:
+            os.environ["CLIPX_TOWER_STREAMS"] = prev_streams
+        achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
 
     if rank == 0:
         print(f"[bench] timed region done: {ms:.1f} ms/step", file=sys.stderr, flush=True)
@@ -492,23 +498,24 @@ def main():
                        "grad_checkpointing": bool(args.grad_checkpointing),
                        "tower_streams": 1 if os.environ.get("CLIPX_TOWER_STREAMS", "1") == "0" else 2,
                        "text_rows": text_rows, "lr": "5e-4, 2000-step warm-up"},
-            "roofline": {"bound": "mfma", "kernel": "NT GEMM (gemm_bf16_nt8p_kernel; gemm_bf16_nt_kernel / nt5 for the shapes it does not take)", "achieved": round(achieved, 1),
-                         "peak": PEAK_BF16_DENSE_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_DENSE_TFLOPS, 4),
-                         "traffic": pmc_traffic(args.model, b, args.precision, "packed" if layout is not None else "dense"),
-                         "algorithmic_bytes_per_launch": int(gemm_bytes / max(n_launch, 1)),
-                         "launches_per_step": n_launch, "avg_launch_us": round(gemm_ms * 1e3 / max(n_launch, 1), 1)},
             "first_loss": round(first_loss, 4) if first_loss is not None else None, "final_loss": round(final_loss, 4),
         }
-        if n8 > 0 and flops8 > gemm_flops:
-            ach8 = flops8 / (ms8 * 1e-3) / 1e12
-            res["roofline_bf16_launches"] = {k: res["roofline"][k] for k in ("kernel", "achieved", "peak", "frac", "launches_per_step", "avg_launch_us")}
-            res["roofline"] = {"bound": "mfma", "kernel": "gemm_fp8_nt8p_kernel (e4m3 x e4m3 on v_mfma_f32_16x16x128_f8f6f4: forward linears + dgrads of the residual blocks)",
-                               "achieved": round(ach8, 1), "peak": PEAK_FP8_DENSE_TFLOPS, "unit": "TFLOP/s",
-                               "frac": round(ach8 / PEAK_FP8_DENSE_TFLOPS, 4), "traffic": None,
-                               "algorithmic_bytes_per_launch": int(bytes8 / n8), "launches_per_step": n8,
-                               "avg_launch_us": round(ms8 * 1e3 / n8, 1)}
-        if res["roofline"]["traffic"]:
-            res["roofline"]["traffic_over_algorithmic"] = round(res["roofline"]["traffic"] / max(1, res["roofline"]["algorithmic_bytes_per_launch"]), 3)
+        if args.full:
+            res["roofline"] = {"bound": "mfma", "kernel": "NT GEMM (gemm_bf16_nt8p_kernel; gemm_bf16_nt_kernel / nt5 for the shapes it does not take)", "achieved": round(achieved, 1),
+                               "peak": PEAK_BF16_DENSE_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_DENSE_TFLOPS, 4),
+                               "traffic": pmc_traffic(args.model, b, args.precision, "packed" if layout is not None else "dense"),
+                               "algorithmic_bytes_per_launch": int(gemm_bytes / max(n_launch, 1)),
+                               "launches_per_step": n_launch, "avg_launch_us": round(gemm_ms * 1e3 / max(n_launch, 1), 1)}
+            if n8 > 0 and flops8 > gemm_flops:
+                ach8 = flops8 / (ms8 * 1e-3) / 1e12
+                res["roofline_bf16_launches"] = {k: res["roofline"][k] for k in ("kernel", "achieved", "peak", "frac", "launches_per_step", "avg_launch_us")}
+                res["roofline"] = {"bound": "mfma", "kernel": "gemm_fp8_nt8p_kernel (e4m3 x e4m3 on v_mfma_f32_16x16x128_f8f6f4: forward linears + dgrads of the residual blocks)",
+                                   "achieved": round(ach8, 1), "peak": PEAK_FP8_DENSE_TFLOPS, "unit": "TFLOP/s",
+                                   "frac": round(ach8 / PEAK_FP8_DENSE_TFLOPS, 4), "traffic": None,
+                                   "algorithmic_bytes_per_launch": int(bytes8 / n8), "launches_per_step": n8,
+                                   "avg_launch_us": round(ms8 * 1e3 / n8, 1)}
+            if res["roofline"]["traffic"]:
+                res["roofline"]["traffic_over_algorithmic"] = round(res["roofline"]["traffic"] / max(1, res["roofline"]["algorithmic_bytes_per_launch"]), 3)
         if dense is not None:
             # positions behind a caption's EOT cannot reach the loss (causal mask + EOT pooling) and get a zero gradient:
             # `value` computes only the live positions; this is the same step computing all 77 like the reference does
@@ -523,7 +530,7 @@ def main():
                                     "frac": round(ips * executed * 1e9 / 1e12 / world / PEAK_BF16_DENSE_TFLOPS, 4),
                                     "flops_per_pair_executed": round(executed * 1e9), "flops_per_pair_dense_reference": gf * 1e9,
                                     "dense_equivalent_tflops_per_gpu": round(step_tf, 1)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(args.cpu_steps)
         print(json.dumps(res), flush=True)
     if world > 1 or args.force_dist:

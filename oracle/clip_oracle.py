@@ -3,7 +3,7 @@
 A plain-PyTorch (fp32, CPU) restatement of the reference's CLIP train-step hot
 path, written as explicit tensor math (no nn.MultiheadAttention, no nn.Conv2d) so
 every line can be compared with the HIP kernels.  Only `tests/`,
-`__graft_entry__.smoke()` and `bench.py`'s `cpu_baseline` leg may import this.
+`__graft_entry__.smoke()` and `bench.py --full`'s `cpu_baseline` leg may import this.
 
 Pinning: the reference ships no tests or golden vectors, so this
 restatement is pinned by fixtures generated in the build container by importing

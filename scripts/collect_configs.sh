@@ -9,8 +9,8 @@ F=gpurun_out/final_$ROUND
 mkdir -p $F
 prof_cfg() {   # tag, steps profiled, bench flags...
   local tag=$1 n=$2; shift 2
-  python bench.py "$@" --steps $n --warmup 1 --no-cpu-baseline --no-dense-compare > $F/bench_$tag.json 2> $F/bench_$tag.err; echo "$tag rc=$?"; tail -c 600 $F/bench_$tag.json
-  (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$F/prof_$tag -- python3 $ROOT/bench.py "$@" --serial-towers --steps $n --warmup 1 --no-cpu-baseline --no-dense-compare > $ROOT/$F/prof_$tag.log 2>&1)
+  python bench.py "$@" --steps $n --warmup 1 --full --no-cpu-baseline --no-dense-compare > $F/bench_$tag.json 2> $F/bench_$tag.err; echo "$tag rc=$?"; tail -c 600 $F/bench_$tag.json
+  (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$F/prof_$tag -- python3 $ROOT/bench.py "$@" --serial-towers --steps $n --warmup 1 --full --no-cpu-baseline --no-dense-compare > $ROOT/$F/prof_$tag.log 2>&1)
   python scripts/kstats.py $F/prof_$tag $((n + 2)) 0.05 > $F/kstats_$tag.txt; head -12 $F/kstats_$tag.txt
 }
 prof_cfg b16_b512 10 --model ViT-B-16 --global-batch 512

@@ -12,7 +12,7 @@ R=${ROUND:-r04}
 OUT=$ROOT/gpurun_out/pmc_$R
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --serial-towers --steps 1 --warmup 1 --no-cpu-baseline --no-dense-compare $*"
+BENCH="python3 $ROOT/bench.py --serial-towers --steps 1 --warmup 1 --full --no-cpu-baseline --no-dense-compare $*"
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE \
           --kernel-trace --output-format csv -d $OUT/sq -- $BENCH > $OUT/sq.log 2>&1
 echo "sq pass rc=$?"

@@ -37,3 +37,27 @@ def test_bench_dump_outputs_repeat(tmp_path):
     differ = [k for k in a if a[k].shape != b[k].shape or not np.array_equal(a[k], b[k])]
     assert all(np.isfinite(x).all() for x in a.values())
     assert not differ, differ[:10]
+
+
+def _result_line(*extra):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--global-batch", "64", *extra]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_bench_full_adds_its_own_runs():
+    """A plain run stops after the timed steps; --full adds the dense-text measurement, the instrumented step behind `roofline`
+    and the CPU baseline."""
+    full_only = {"dense_text_rows", "roofline", "cpu_baseline"}
+    plain = _result_line()
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(plain) and plain["value"] > 0
+    assert not full_only & set(plain), sorted(full_only & set(plain))
+    full = _result_line("--full", "--cpu-steps", "1")
+    assert full_only <= set(full), sorted(full_only - set(full))
+    assert full["dense_text_rows"]["steps"] == 2 and full["dense_text_rows"]["ms_per_step"] > 0
+    assert full["roofline"]["launches_per_step"] > 0 and full["roofline"]["achieved"] > 0
+    assert full["cpu_baseline"]["value"] > 0
