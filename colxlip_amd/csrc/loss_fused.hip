@@ -11,33 +11,12 @@
 //             Scratch: (N/64) x N x 2 floats per direction (2 MiB at N = 4096), O(N^2 / 64).
 //   backward  one launch per operand: a block owns 64 rows of that operand, walks the other side's 64-row tiles,
 //             recomputes the logits tile, forms d(logits) from the saved log-sum-exps and accumulates
-//             d(logits) . Q_tile into 64 x E registers; the walk is split over SPLIT blocks (fp32 atomics merge).
+//             d(logits) . Q_tile into 64 x E registers; the walk is split over SPLIT blocks whose partials are summed in a
+//             fixed order (no atomics: the same result every run).
 // FLOPs: 1 (forward) + 2 x 2 (two backward passes, each recompute + product) = 5 logits-GEMM equivalents instead of 3
 // with the matrix in memory: at N = 4096, E = 512 that is 86 GFLOP = 0.55 ms at the 157 TF fp32-MFMA peak.
-#include "kernels.h"
-
-#define LF_T 64              // tile edge (rows of P x rows of Q)
-#define LF_BK 64             // k-depth of one staged chunk (16 was latency-bound: two barriers + an L2 round trip per 16-deep chunk)
-#define LF_LD (LF_T + 16)    // LDS row stride of the k-major operand images (as gemm_f32.hip)
-
-// stage rows [r0, r0+64) x columns [k0, k0+64) of a row-major [n, E] matrix into the k-major LDS image S[k][row]
-// (16-byte loads, four per thread, all issued before the first LDS write; rows >= n and columns >= E read as zero)
-__device__ __forceinline__ void lf_stage(float (&S)[LF_BK][LF_LD], const float* __restrict__ src, int r0, int n, int E, int k0,
-                                         int tid) {
-    const int k4 = (tid & 15) * 4;
-    float4 v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = (tid >> 4) + 16 * i;
-        v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (r0 + m < n && k0 + k4 < E) v[i] = load4(src + (long)(r0 + m) * E + k0 + k4);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = (tid >> 4) + 16 * i;
-        S[k4][m] = v[i].x; S[k4 + 1][m] = v[i].y; S[k4 + 2][m] = v[i].z; S[k4 + 3][m] = v[i].w;
-    }
-}
+// The tile engine (staging, tiles, walk, product, fixed-order sums, embed dims) is loss_tile.h.
+#include "loss_tile.h"
 
 // ---------------------------------------------------------------------------------------------- forward
 __global__ __launch_bounds__(256) void ce_fused_fwd_kernel(int np, int nq, int E, const float* __restrict__ P,
@@ -45,45 +24,17 @@ __global__ __launch_bounds__(256) void ce_fused_fwd_kernel(int np, int nq, int E
                                                            float* __restrict__ row_m, float* __restrict__ row_l,
                                                            float* __restrict__ col_m, float* __restrict__ col_l,
                                                            float* __restrict__ zdiag) {
-    __shared__ float Ps[LF_BK][LF_LD];
-    __shared__ float Qs[LF_BK][LF_LD];
-    __shared__ float Zs[LF_T][LF_T + 1];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int g = lane >> 4, c = lane & 15;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int p0 = blockIdx.y * LF_T, q0 = blockIdx.x * LF_T;
-    f32x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int k0 = 0; k0 < E; k0 += LF_BK) {
-        lf_stage(Ps, P, p0, np, E, k0, tid);
-        lf_stage(Qs, Q, q0, nq, E, k0, tid);
-        __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < LF_BK / 4; ++ks) {
-            const float a0 = Ps[ks * 4 + g][wm * 32 + c], a1 = Ps[ks * 4 + g][wm * 32 + 16 + c];
-            const float b0 = Qs[ks * 4 + g][wn * 32 + c], b1 = Qs[ks * 4 + g][wn * 32 + 16 + c];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    // C/D map of the 16x16 MFMA: col = lane & 15, row = 4*(lane >> 4) + reg
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Zs[wm * 32 + 16 * i + 4 * g + r][wn * 32 + 16 * j + c] = acc[i][j][r];
+    __shared__ float Ps[LT_BK][LT_LD];
+    __shared__ float Qs[LT_BK][LT_LD];
+    __shared__ float Zs[LT_T][LT_T + 1];
+    const int tid = threadIdx.x;
+    const int p0 = blockIdx.y * LT_T, q0 = blockIdx.x * LT_T;
+    lt_tile_to_lds(Ps, Qs, Zs, P, Q, p0, np, q0, nq, E, tid);
     __syncthreads();
-    if (tid < LF_T) {                       // one thread per tile row: (max, sum exp) over the tile's valid columns
+    if (tid < LT_T) {                       // one thread per tile row: (max, sum exp) over the tile's valid columns
         const int p = p0 + tid;
         if (p < np) {
-            const int nvalid = min(LF_T, nq - q0);
+            const int nvalid = min(LT_T, nq - q0);
             float m = -INFINITY;
             for (int j = 0; j < nvalid; ++j) m = fmaxf(m, Zs[tid][j]);
             float l = 0.f;
@@ -93,10 +44,10 @@ __global__ __launch_bounds__(256) void ce_fused_fwd_kernel(int np, int nq, int E
             const int lab = p + label_off - q0;
             if (lab >= 0 && lab < nvalid) zdiag[p] = Zs[tid][lab];
         }
-    } else if (symmetric && tid < 2 * LF_T) {   // one thread per tile column
-        const int j = tid - LF_T, q = q0 + j;
+    } else if (symmetric && tid < 2 * LT_T) {   // one thread per tile column
+        const int j = tid - LT_T, q = q0 + j;
         if (q < nq) {
-            const int nvalid = min(LF_T, np - p0);
+            const int nvalid = min(LT_T, np - p0);
             float m = -INFINITY;
             for (int i = 0; i < nvalid; ++i) m = fmaxf(m, Zs[i][j]);
             float l = 0.f;
@@ -130,15 +81,8 @@ __global__ __launch_bounds__(256) void ce_fused_merge_kernel(int n, int ntiles, 
     if (threadIdx.x == 0) loss_part[blockIdx.x] = weight * ((part[0] + part[1]) + (part[2] + part[3]));
 }
 
-// *acc += sum_i part[i] in index order (one thread: the block partials of a loss or d(scale) add up the same way every run)
-__global__ void ce_sum_parts_kernel(int n, const float* __restrict__ part, float* __restrict__ acc) {
-    float s = 0.f;
-    for (int i = 0; i < n; ++i) s += part[i];
-    *acc += s;
-}
-
 extern "C" size_t clipx_ce_fused_ws_bytes(int np, int nq, int symmetric) {
-    const size_t tq = (nq + LF_T - 1) / LF_T, tp = (np + LF_T - 1) / LF_T;
+    const size_t tq = (nq + LT_T - 1) / LT_T, tp = (np + LT_T - 1) / LT_T;
     size_t f = 2 * tq * (size_t)np + (size_t)max(np, nq);                 // row partials + label logits
     if (symmetric) f += 2 * tp * (size_t)nq;
     f += (size_t)cdiv(np, 256) + (symmetric ? (size_t)cdiv(nq, 256) : 0);   // loss partials of the merge blocks
@@ -152,7 +96,7 @@ extern "C" int clipx_ce_fused_fwd(int np, int nq, int E, const float* P, const f
     CLIPX_CHECK(label_off >= 0 && np + label_off <= nq, "ce_fused_fwd: labels out of range");
     CLIPX_CHECK(!symmetric || (np == nq && label_off == 0), "ce_fused_fwd: the symmetric form needs a square problem");
     CLIPX_CHECK(ws_bytes >= clipx_ce_fused_ws_bytes(np, nq, symmetric), "ce_fused_fwd: workspace too small");
-    const int tq = cdiv(nq, LF_T), tp = cdiv(np, LF_T);
+    const int tq = cdiv(nq, LT_T), tp = cdiv(np, LT_T);
     float* row_m = (float*)ws;
     float* row_l = row_m + (size_t)tq * np;
     float* zdiag = row_l + (size_t)tq * np;
@@ -166,8 +110,8 @@ extern "C" int clipx_ce_fused_fwd(int np, int nq, int E, const float* P, const f
     if (symmetric)
         hipLaunchKernelGGL(ce_fused_merge_kernel, dim3(cdiv(nq, 256)), dim3(256), 0, (hipStream_t)stream, nq, tp, col_m,
                            col_l, zdiag, w_oth, lse_oth, loss_part + cdiv(np, 256));
-    hipLaunchKernelGGL(ce_sum_parts_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream,
-                       cdiv(np, 256) + (symmetric ? cdiv(nq, 256) : 0), loss_part, loss_acc);
+    hipLaunchKernelGGL(lt_sum_parts_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream,
+                       cdiv(np, 256) + (symmetric ? cdiv(nq, 256) : 0), 1, loss_part, nullptr, loss_acc);
     CLIPX_LAUNCH_CHECK();
     return 0;
 }
@@ -184,20 +128,16 @@ __global__ __launch_bounds__(256, (NE <= 32 ? 2 : 1)) void ce_fused_bwd_kernel(i
                                                            float out_scale_mul, const float* __restrict__ gout_dev,
                                                            float* __restrict__ dP_part, float* __restrict__ ds_part_out,
                                                            const float* __restrict__ scale_dev) {
-    constexpr int E = 16 * NE;
-    constexpr int EC = (NE >= 4) ? 64 : 16 * NE;     // columns of Q staged per chunk of the product
-    constexpr int TC = EC / 16;                      // accumulator tiles per chunk
-    __shared__ float Ps[LF_BK][LF_LD];
-    __shared__ float Qs[LF_BK][LF_LD];
-    __shared__ float dZs[LF_T][LF_T + 2];      // stride 66: the A-operand read (row = lane & 15, k = lane >> 4) is conflict-free
-    __shared__ float Qe[LF_T][EC + 16];        // stride == 16 (mod 32), as the k-major operand images
+    __shared__ float Ps[LT_BK][LT_LD];
+    __shared__ float Qs[LT_BK][LT_LD];
+    __shared__ float dZs[LT_T][LT_T + 2];
+    __shared__ float Qe[LT_T][lt_ec(NE) + 16];
     __shared__ float red[4];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int g = lane >> 4, c = lane & 15;
-    const int p0 = blockIdx.x * LF_T;
-    const int ntq = (nq + LF_T - 1) / LF_T;
-    const int per = (ntq + gridDim.y - 1) / gridDim.y;
-    const int jt0 = blockIdx.y * per, jt1 = min(ntq, jt0 + per);
+    const int p0 = blockIdx.x * LT_T;
+    int jt0, jt1;
+    lt_split_range(nq, jt0, jt1);
 
     f32x4 acc[NE];
 #pragma unroll
@@ -213,24 +153,9 @@ __global__ __launch_bounds__(256, (NE <= 32 ? 2 : 1)) void ce_fused_bwd_kernel(i
     float ds_part = 0.f;
 
     for (int jt = jt0; jt < jt1; ++jt) {
-        const int q0 = jt * LF_T;
-        // ---- logits tile: wave w owns rows 16w..16w+15 against the tile's four 16-column groups
+        const int q0 = jt * LT_T;
         f32x4 z[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) z[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        for (int k0 = 0; k0 < E; k0 += LF_BK) {
-            lf_stage(Ps, P, p0, np, E, k0, tid);
-            lf_stage(Qs, Q, q0, nq, E, k0, tid);
-            __syncthreads();
-#pragma unroll
-            for (int ks = 0; ks < LF_BK / 4; ++ks) {
-                const float a = Ps[ks * 4 + g][16 * wave + c];
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-                    z[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Qs[ks * 4 + g][16 * t + c], z[t], 0, 0, 0);
-            }
-            __syncthreads();
-        }
+        lt_slab(z, Ps, Qs, P, Q, p0, np, q0, nq, 16 * NE, tid, wave, g, c);
         // ---- d(logits) for this wave's 16 x 64 slice -> LDS (read back as the A operand of the product)
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -249,91 +174,22 @@ __global__ __launch_bounds__(256, (NE <= 32 ? 2 : 1)) void ce_fused_bwd_kernel(i
                 dZs[16 * wave + 4 * g + r][16 * t + c] = d;
             }
         }
-        // ---- product: acc[16 rows x E] += dZ[16 x 64] . Q_tile[64 x E], Q staged EC columns at a time
-#pragma unroll
-        for (int ec = 0; ec < NE / TC; ++ec) {
-            __syncthreads();                            // Qe free (previous chunk consumed); dZs rows of this wave written
-            for (int i = tid; i < LF_T * (EC / 4); i += 256) {
-                const int row = i / (EC / 4), c4 = (i % (EC / 4)) * 4;
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (q0 + row < nq) v = load4(Q + (long)(q0 + row) * E + ec * EC + c4);
-                Qe[row][c4] = v.x; Qe[row][c4 + 1] = v.y; Qe[row][c4 + 2] = v.z; Qe[row][c4 + 3] = v.w;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int kc = 0; kc < LF_T / 4; ++kc) {
-                const float a = dZs[16 * wave + c][4 * kc + g];
-#pragma unroll
-                for (int t = 0; t < TC; ++t)
-                    acc[ec * TC + t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Qe[4 * kc + g][16 * t + c], acc[ec * TC + t], 0, 0, 0);
-            }
-        }
-        __syncthreads();
+        lt_product<NE>(acc, dZs, Qe, Q, q0, nq, tid, wave, g, c);
     }
-    // ---- write-out: this block's share of dP (the walk over q tiles is split over gridDim.y blocks): dP_part[blockIdx.y][p][e],
-    // summed over the splits in split order by ce_split_sum_kernel (no atomics: the same dP every run)
+    // the split partial is scaled here, before the split sum; d(scale) is divided by the scale per block
     float osc = out_scale_mul;
     if (out_scale_dev) osc *= out_scale_dev[0];
     if (gout_dev) osc *= gout_dev[0];
-#pragma unroll
-    for (int t = 0; t < NE; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int p = prow[r];
-            if (p < np) dP_part[((long)blockIdx.y * np + p) * E + 16 * t + c] = osc * acc[t][r];
-        }
+    lt_store_part<NE>(dP_part, acc, prow, np, osc, c);
     if (ds_part_out) {
-        ds_part = wave_sum(ds_part);
-        if (lane == 0) red[wave] = ds_part;
-        __syncthreads();
-        if (tid == 0)
-            ds_part_out[blockIdx.y * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) / scale_dev[0];
+        const float v = lt_block_sum(ds_part, red, wave, lane);
+        if (tid == 0) ds_part_out[blockIdx.y * gridDim.x + blockIdx.x] = v / scale_dev[0];
     }
-}
-
-// out[j] = sum_s part[s*n + j], s in order
-__global__ __launch_bounds__(256) void ce_split_sum_kernel(int nsplit, long n, const float* __restrict__ part,
-                                                           float* __restrict__ out) {
-    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < n; j += (long)gridDim.x * 256) {
-        float s = 0.f;
-        for (int k = 0; k < nsplit; ++k) s += part[k * n + j];
-        out[j] = s;
-    }
-}
-
-// blocks over the q tiles of one row tile: ~3 blocks per CU in flight
-static int ce_bwd_split(int np, int nq) {
-    const int tp = cdiv(np, LF_T), tq = cdiv(nq, LF_T);
-    int split = cdiv(768, tp);
-    if (split > tq) split = tq;
-    if (split < 1) split = 1;
-    return split;
 }
 
 extern "C" size_t clipx_ce_fused_bwd_ws_bytes(int np, int nq, int E) {
-    const size_t split = ce_bwd_split(np, nq);
-    return (split * (size_t)np * E + split * (size_t)cdiv(np, LF_T)) * sizeof(float);
-}
-
-template <int NE>
-static int launch_ce_bwd(int np, int nq, const float* P, const float* Q, const float* lse_own, float w_own, int off_own,
-                         const float* lse_oth, float w_oth, int off_oth, const float* out_scale_dev, float out_scale_mul,
-                         const float* gout_dev, float* dP, float* dscale_acc, const float* scale_dev, float* ws,
-                         hipStream_t stream) {
-    const int tp = cdiv(np, LF_T);
-    const int split = ce_bwd_split(np, nq);
-    const long n = (long)np * 16 * NE;
-    float* dP_part = ws;
-    float* ds_part = ws + (size_t)split * n;
-    hipLaunchKernelGGL(ce_fused_bwd_kernel<NE>, dim3(tp, split), dim3(256), 0, stream, np, nq, P, Q, lse_own, w_own, off_own,
-                       lse_oth, w_oth, off_oth, out_scale_dev, out_scale_mul, gout_dev, dP_part,
-                       dscale_acc ? ds_part : nullptr, scale_dev);
-    int grid = cdiv(n, 256);
-    if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(ce_split_sum_kernel, dim3(grid), dim3(256), 0, stream, split, n, dP_part, dP);
-    if (dscale_acc) hipLaunchKernelGGL(ce_sum_parts_kernel, dim3(1), dim3(1), 0, stream, tp * split, ds_part, dscale_acc);
-    CLIPX_LAUNCH_CHECK();
-    return 0;
+    const size_t split = lt_split(np, nq, 768);
+    return (split * (size_t)np * E + split * (size_t)cdiv(np, LT_T)) * sizeof(float);
 }
 
 extern "C" int clipx_ce_fused_bwd(int np, int nq, int E, const float* P, const float* Q, const float* lse_own, float w_own,
@@ -344,12 +200,19 @@ extern "C" int clipx_ce_fused_bwd(int np, int nq, int E, const float* P, const f
     CLIPX_CHECK(ws_bytes >= clipx_ce_fused_bwd_ws_bytes(np, nq, E), "ce_fused_bwd: workspace too small");
     CLIPX_CHECK(lse_own || lse_oth, "ce_fused_bwd: no cross-entropy term");
     CLIPX_CHECK(!dscale_acc || scale_dev, "ce_fused_bwd: d(scale) needs the scale");
-#define LF_CASE(ne)                                                                                                     \
-    if (E == 16 * (ne))                                                                                                 \
-        return launch_ce_bwd<ne>(np, nq, P, Q, lse_own, w_own, off_own, lse_oth, w_oth, off_oth, out_scale_dev,         \
-                                 out_scale_mul, gout_dev, dP, dscale_acc, scale_dev, (float*)ws, (hipStream_t)stream);
-    LF_CASE(1) LF_CASE(2) LF_CASE(4) LF_CASE(8) LF_CASE(16) LF_CASE(32) LF_CASE(40) LF_CASE(48) LF_CASE(64)
-#undef LF_CASE
-    clipx_set_error("ce_fused_bwd: embed dim %d unsupported (16, 32, 64, 128, 256, 512, 640, 768, 1024)", E);
-    return -1;
+    const int tp = cdiv(np, LT_T), split = lt_split(np, nq, 768);
+    const long n = (long)np * E;
+    float* dP_part = (float*)ws;
+    float* ds_part = dP_part + (size_t)split * n;
+    hipStream_t st = (hipStream_t)stream;
+    const int known = fused_dim_dispatch(E, [&](auto ne) {
+        hipLaunchKernelGGL(ce_fused_bwd_kernel<decltype(ne)::value>, dim3(tp, split), dim3(256), 0, st, np, nq, P, Q, lse_own,
+                           w_own, off_own, lse_oth, w_oth, off_oth, out_scale_dev, out_scale_mul, gout_dev, dP_part,
+                           dscale_acc ? ds_part : nullptr, scale_dev);
+    });
+    CLIPX_CHECK(known == 0, "ce_fused_bwd: embed dim %d unsupported (" LT_FUSED_DIMS_STR ")", E);
+    lt_split_sum(split, n, dP_part, nullptr, nullptr, 0, dP, st);
+    if (dscale_acc) hipLaunchKernelGGL(lt_sum_parts_kernel, dim3(1), dim3(1), 0, st, tp * split, 1, ds_part, nullptr, dscale_acc);
+    CLIPX_LAUNCH_CHECK();
+    return 0;
 }

@@ -14,30 +14,8 @@
 // FLOPs: 2 (forward: recompute + product) + 2 (backward) = 4 logits-GEMM equivalents, against the CE path's 5.
 // The walks are split over gridDim.y blocks; split partials and block partials are summed in a fixed order (no atomics:
 // the same result every run).  Embed dims outside ops.FUSED_CE_DIMS run sig_dense_kernel on a materialised logits matrix.
-#include "kernels.h"
-
-#define LS_T 64              // tile edge
-#define LS_BK 64             // k-depth of one staged chunk
-#define LS_LD (LS_T + 16)    // LDS row stride of the k-major operand images
-
-// stage rows [r0, r0+64) x columns [k0, k0+64) of a row-major [n, E] matrix into the k-major LDS image S[k][row]
-// (rows >= n and columns >= E read as zero)
-__device__ __forceinline__ void ls_stage(float (&S)[LS_BK][LS_LD], const float* __restrict__ src, int r0, int n, int E, int k0,
-                                         int tid) {
-    const int k4 = (tid & 15) * 4;
-    float4 v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = (tid >> 4) + 16 * i;
-        v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (r0 + m < n && k0 + k4 < E) v[i] = load4(src + (long)(r0 + m) * E + k0 + k4);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = (tid >> 4) + 16 * i;
-        S[k4][m] = v[i].x; S[k4 + 1][m] = v[i].y; S[k4 + 2][m] = v[i].z; S[k4 + 3][m] = v[i].w;
-    }
-}
+// The tile engine is loss_tile.h.
+#include "loss_tile.h"
 
 // one logit's share: x = -y z;  softplus(x) = max(x, 0) + log1p(exp(-|x|)),  sigmoid(x) = (x >= 0 ? 1 : e) / (1 + e), e = exp(-|x|)
 // (|z| reaches ~110 at the clamped s = 100 with beta = -10: neither form overflows)
@@ -49,15 +27,6 @@ __device__ __forceinline__ float sig_term(float z, bool pos, float inv_r, float&
     return pos ? -inv_r * sg : inv_r * sg;
 }
 
-// block partials -> 4 waves -> one float (fixed order)
-__device__ __forceinline__ float block_sum4(float v, float* red, int wave, int lane) {
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // A block owns rows [p0, p0+64) of P and walks its share of Q's 64-row tiles.  The positive of own row p sits at column
 // q == p + pos_off (transposed: p == q + pos_off, P being the B side).  NE = E / 16 accumulator tiles per wave; NE == 0 is the
 // loss-only walk (no product, E at run time).  dP_part[blockIdx.y][p][e] = sum_q dz(p,q) Q[q,e] over this block's tiles
@@ -67,21 +36,18 @@ __global__ __launch_bounds__(256, (NE <= 32 ? 2 : 1)) void sig_walk_kernel(
         int np, int nq, int E_rt, const float* __restrict__ P, const float* __restrict__ Q, const float* __restrict__ scale_dev,
         const float* __restrict__ bias_dev, int pos_off, int transposed, float inv_r, float* __restrict__ dP_part,
         float* __restrict__ part_loss, float* __restrict__ part_ds, float* __restrict__ part_db) {
-    constexpr int EC = (NE >= 4) ? 64 : (NE > 0 ? 16 * NE : 16);   // columns of Q staged per chunk of the product
-    constexpr int TC = EC / 16;                                     // accumulator tiles per chunk
     constexpr int NACC = NE > 0 ? NE : 1;
     const int E = NE > 0 ? 16 * NE : E_rt;
-    __shared__ float Ps[LS_BK][LS_LD];
-    __shared__ float Qs[LS_BK][LS_LD];
-    __shared__ float dZs[NE > 0 ? LS_T : 1][LS_T + 2];   // stride 66: the A-operand read (row = lane & 15, k = lane >> 4) is conflict-free
-    __shared__ float Qe[NE > 0 ? LS_T : 1][EC + 16];     // stride == 16 (mod 32), as the k-major operand images
+    __shared__ float Ps[LT_BK][LT_LD];
+    __shared__ float Qs[LT_BK][LT_LD];
+    __shared__ float dZs[NE > 0 ? LT_T : 1][LT_T + 2];
+    __shared__ float Qe[NE > 0 ? LT_T : 1][lt_ec(NE) + 16];
     __shared__ float red[4];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int g = lane >> 4, c = lane & 15;
-    const int p0 = blockIdx.x * LS_T;
-    const int ntq = (nq + LS_T - 1) / LS_T;
-    const int per = (ntq + gridDim.y - 1) / gridDim.y;
-    const int jt0 = blockIdx.y * per, jt1 = min(ntq, jt0 + per);
+    const int p0 = blockIdx.x * LT_T;
+    int jt0, jt1;
+    lt_split_range(nq, jt0, jt1);
     const float s = scale_dev[0], beta = bias_dev[0];
 
     f32x4 acc[NACC];
@@ -93,24 +59,9 @@ __global__ __launch_bounds__(256, (NE <= 32 ? 2 : 1)) void sig_walk_kernel(
     float l_part = 0.f, ds_part = 0.f, db_part = 0.f;
 
     for (int jt = jt0; jt < jt1; ++jt) {
-        const int q0 = jt * LS_T;
-        // ---- dot tile: wave w owns rows 16w..16w+15 against the tile's four 16-column groups
+        const int q0 = jt * LT_T;
         f32x4 d[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) d[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        for (int k0 = 0; k0 < E; k0 += LS_BK) {
-            ls_stage(Ps, P, p0, np, E, k0, tid);
-            ls_stage(Qs, Q, q0, nq, E, k0, tid);
-            __syncthreads();
-#pragma unroll
-            for (int ks = 0; ks < LS_BK / 4; ++ks) {
-                const float a = Ps[ks * 4 + g][16 * wave + c];
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-                    d[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Qs[ks * 4 + g][16 * t + c], d[t], 0, 0, 0);
-            }
-            __syncthreads();
-        }
+        lt_slab(d, Ps, Qs, P, Q, p0, np, q0, nq, E, tid, wave, g, c);
         // ---- epilogue on this wave's 16 x 64 slice (C/D map: col = lane & 15, row = 4*(lane >> 4) + reg)
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -129,49 +80,20 @@ __global__ __launch_bounds__(256, (NE <= 32 ? 2 : 1)) void sig_walk_kernel(
                 if constexpr (NE > 0) dZs[16 * wave + 4 * g + r][16 * t + c] = dz;
             }
         }
-        if constexpr (NE > 0) {
-            // ---- product: acc[16 rows x E] += dZ[16 x 64] . Q_tile[64 x E], Q staged EC columns at a time
-#pragma unroll
-            for (int ec = 0; ec < NE / TC; ++ec) {
-                __syncthreads();                            // Qe free (previous chunk consumed); dZs rows of this wave written
-                for (int i = tid; i < LS_T * (EC / 4); i += 256) {
-                    const int row = i / (EC / 4), c4 = (i % (EC / 4)) * 4;
-                    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (q0 + row < nq) v = load4(Q + (long)(q0 + row) * E + ec * EC + c4);
-                    Qe[row][c4] = v.x; Qe[row][c4 + 1] = v.y; Qe[row][c4 + 2] = v.z; Qe[row][c4 + 3] = v.w;
-                }
-                __syncthreads();
-#pragma unroll
-                for (int kc = 0; kc < LS_T / 4; ++kc) {
-                    const float a = dZs[16 * wave + c][4 * kc + g];
-#pragma unroll
-                    for (int t = 0; t < TC; ++t)
-                        acc[ec * TC + t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Qe[4 * kc + g][16 * t + c], acc[ec * TC + t], 0, 0, 0);
-                }
-            }
-            __syncthreads();
-        }
+        if constexpr (NE > 0) lt_product<NE>(acc, dZs, Qe, Q, q0, nq, tid, wave, g, c);
     }
-    if constexpr (NE > 0) {
-#pragma unroll
-        for (int t = 0; t < NE; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int p = prow[r];
-                if (p < np) dP_part[((long)blockIdx.y * np + p) * E + 16 * t + c] = acc[t][r];
-            }
-    }
+    if constexpr (NE > 0) lt_store_part<NE>(dP_part, acc, prow, np, 1.f, c);
     const int bid = blockIdx.y * gridDim.x + blockIdx.x;
     if (part_loss) {
-        const float v = block_sum4(l_part, red, wave, lane);
+        const float v = lt_block_sum(l_part, red, wave, lane);
         if (tid == 0) part_loss[bid] = v;
     }
     if (part_ds) {
-        const float v = block_sum4(ds_part, red, wave, lane);
+        const float v = lt_block_sum(ds_part, red, wave, lane);
         if (tid == 0) part_ds[bid] = v;
     }
     if (part_db) {
-        const float v = block_sum4(db_part, red, wave, lane);
+        const float v = lt_block_sum(db_part, red, wave, lane);
         if (tid == 0) part_db[bid] = v;
     }
 }
@@ -189,71 +111,28 @@ __global__ void sig_sum3_kernel(int n, const float* __restrict__ part_loss, cons
     out3[k] = accumulate ? out3[k] + v : v;
 }
 
-// out[j] = (accumulate ? out[j] : 0) + s * (gout) * sum_k part[k*n + j], k in order
-__global__ __launch_bounds__(256) void sig_split_sum_kernel(int nsplit, long n, const float* __restrict__ part,
-                                                            const float* __restrict__ scale_dev, const float* __restrict__ gout_dev,
-                                                            int accumulate, float* __restrict__ out) {
-    float osc = scale_dev[0];
-    if (gout_dev) osc *= gout_dev[0];
-    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < n; j += (long)gridDim.x * 256) {
-        float sum = 0.f;
-        for (int k = 0; k < nsplit; ++k) sum += part[k * n + j];
-        out[j] = accumulate ? out[j] + osc * sum : osc * sum;
-    }
-}
-
 // blocks over the q tiles of one row tile: ~3 blocks per CU in flight for the product walks, more for the loss-only walk
-static int sig_split(int np, int nq, bool grad) {
-    const int tp = cdiv(np, LS_T), tq = cdiv(nq, LS_T);
-    int split = cdiv(grad ? 768 : 2048, tp);
-    if (split > tq) split = tq;
-    if (split < 1) split = 1;
-    return split;
-}
-
-static bool sig_dim_ok(int E) {
-    return E == 16 || E == 32 || E == 64 || E == 128 || E == 256 || E == 512 || E == 640 || E == 768 || E == 1024;
-}
+static int sig_split(int np, int nq, bool grad) { return lt_split(np, nq, grad ? 768 : 2048); }
 
 // workspace: dP split partials (grad) + three arrays of block partials
 static size_t sig_ws_floats(int np, int nq, int E, bool grad) {
-    const size_t split = sig_split(np, nq, grad), nb = split * (size_t)cdiv(np, LS_T);
+    const size_t split = sig_split(np, nq, grad), nb = split * (size_t)cdiv(np, LT_T);
     return (grad ? split * (size_t)np * E : 0) + 3 * nb;
-}
-
-template <int NE>
-static void launch_sig_walk(dim3 grid, hipStream_t stream, int np, int nq, int E, const float* P, const float* Q,
-                            const float* scale_dev, const float* bias_dev, int pos_off, int transposed, float inv_r,
-                            float* dP_part, float* pl, float* pds, float* pdb) {
-    hipLaunchKernelGGL(sig_walk_kernel<NE>, grid, dim3(256), 0, stream, np, nq, E, P, Q, scale_dev, bias_dev, pos_off, transposed,
-                       inv_r, dP_part, pl, pds, pdb);
 }
 
 static int sig_walk(int np, int nq, int E, const float* P, const float* Q, const float* scale_dev, const float* bias_dev,
                     int pos_off, int transposed, float inv_r, float* dP_part, float* pl, float* pds, float* pdb, bool grad,
                     hipStream_t stream) {
-    const dim3 grid(cdiv(np, LS_T), sig_split(np, nq, grad));
+    const dim3 grid(cdiv(np, LT_T), sig_split(np, nq, grad));
+    auto launch = [&](auto ne) {
+        hipLaunchKernelGGL(sig_walk_kernel<decltype(ne)::value>, grid, dim3(256), 0, stream, np, nq, E, P, Q, scale_dev, bias_dev,
+                           pos_off, transposed, inv_r, dP_part, pl, pds, pdb);
+    };
     if (!grad) {
-        launch_sig_walk<0>(grid, stream, np, nq, E, P, Q, scale_dev, bias_dev, pos_off, transposed, inv_r, nullptr, pl, pds, pdb);
+        launch(std::integral_constant<int, 0>{});
         return 0;
     }
-#define LS_CASE(ne)                                                                                                          \
-    if (E == 16 * (ne)) {                                                                                                    \
-        launch_sig_walk<ne>(grid, stream, np, nq, E, P, Q, scale_dev, bias_dev, pos_off, transposed, inv_r, dP_part, pl, pds, \
-                            pdb);                                                                                            \
-        return 0;                                                                                                            \
-    }
-    LS_CASE(1) LS_CASE(2) LS_CASE(4) LS_CASE(8) LS_CASE(16) LS_CASE(32) LS_CASE(40) LS_CASE(48) LS_CASE(64)
-#undef LS_CASE
-    return -1;
-}
-
-static int sig_split_sum(int split, long n, const float* part, const float* scale_dev, const float* gout_dev, int accumulate,
-                         float* out, hipStream_t stream) {
-    int grid = cdiv(n, 256);
-    if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(sig_split_sum_kernel, dim3(grid), dim3(256), 0, stream, split, n, part, scale_dev, gout_dev, accumulate, out);
-    return 0;
+    return fused_dim_dispatch(E, launch);
 }
 
 extern "C" size_t clipx_sigmoid_fused_ws_bytes(int r, int c, int E, int grad) {
@@ -264,11 +143,11 @@ extern "C" int clipx_sigmoid_fused_fwd(int r, int c, int E, const float* A, cons
                                        const float* bias_dev, int pos_off, float inv_r, float* out3, float* dA,
                                        int accumulate, void* ws, size_t ws_bytes, void* stream) {
     CLIPX_CHECK(r > 0 && c > 0 && E > 0, "sigmoid_fused_fwd: empty problem");
-    CLIPX_CHECK(sig_dim_ok(E), "sigmoid_fused_fwd: embed dim %d unsupported (16, 32, 64, 128, 256, 512, 640, 768, 1024)", E);
+    CLIPX_CHECK(is_fused_dim(E), "sigmoid_fused_fwd: embed dim %d unsupported (" LT_FUSED_DIMS_STR ")", E);
     CLIPX_CHECK(pos_off < 0 || r + pos_off <= c, "sigmoid_fused_fwd: positives out of range");
     const bool grad = dA != nullptr;
     CLIPX_CHECK(ws_bytes >= clipx_sigmoid_fused_ws_bytes(r, c, E, grad), "sigmoid_fused_fwd: workspace too small");
-    const int split = sig_split(r, c, grad), nb = split * cdiv(r, LS_T);
+    const int split = sig_split(r, c, grad), nb = split * cdiv(r, LT_T);
     float* dA_part = (float*)ws;
     float* pl = dA_part + (grad ? (size_t)split * r * E : 0);
     float* pds = pl + nb;
@@ -276,7 +155,7 @@ extern "C" int clipx_sigmoid_fused_fwd(int r, int c, int E, const float* A, cons
     hipStream_t st = (hipStream_t)stream;
     sig_walk(r, c, E, A, B, scale_dev, bias_dev, pos_off, 0, inv_r, dA_part, pl, grad ? pds : nullptr, grad ? pdb : nullptr,
              grad, st);
-    if (grad) sig_split_sum(split, (long)r * E, dA_part, scale_dev, nullptr, accumulate, dA, st);
+    if (grad) lt_split_sum(split, (long)r * E, dA_part, scale_dev, nullptr, accumulate, dA, st);
     hipLaunchKernelGGL(sig_sum3_kernel, dim3(1), dim3(64), 0, st, nb, pl, grad ? pds : nullptr, grad ? pdb : nullptr, inv_r,
                        accumulate, out3);
     CLIPX_LAUNCH_CHECK();
@@ -292,7 +171,7 @@ extern "C" int clipx_sigmoid_fused_bwd(int r, int c, int E, const float* A, cons
                                        const float* bias_dev, int pos_off, float inv_r, const float* gout_dev, float* dB,
                                        int accumulate, void* ws, size_t ws_bytes, void* stream) {
     CLIPX_CHECK(r > 0 && c > 0 && E > 0, "sigmoid_fused_bwd: empty problem");
-    CLIPX_CHECK(sig_dim_ok(E), "sigmoid_fused_bwd: embed dim %d unsupported (16, 32, 64, 128, 256, 512, 640, 768, 1024)", E);
+    CLIPX_CHECK(is_fused_dim(E), "sigmoid_fused_bwd: embed dim %d unsupported (" LT_FUSED_DIMS_STR ")", E);
     CLIPX_CHECK(pos_off < 0 || r + pos_off <= c, "sigmoid_fused_bwd: positives out of range");
     CLIPX_CHECK(ws_bytes >= clipx_sigmoid_fused_bwd_ws_bytes(r, c, E), "sigmoid_fused_bwd: workspace too small");
     const int split = sig_split(c, r, true);
@@ -300,7 +179,7 @@ extern "C" int clipx_sigmoid_fused_bwd(int r, int c, int E, const float* A, cons
     hipStream_t st = (hipStream_t)stream;
     // rows of B own the walk: the positive of B row j is A row j - pos_off
     sig_walk(c, r, E, B, A, scale_dev, bias_dev, pos_off, 1, inv_r, dB_part, nullptr, nullptr, nullptr, true, st);
-    sig_split_sum(split, (long)c * E, dB_part, scale_dev, gout_dev, accumulate, dB, st);
+    lt_split_sum(split, (long)c * E, dB_part, scale_dev, gout_dev, accumulate, dB, st);
     CLIPX_LAUNCH_CHECK();
     return 0;
 }
@@ -324,11 +203,11 @@ __global__ __launch_bounds__(256) void sig_dense_kernel(int rows, int cols, floa
             db_part += dz;
             z[(long)i * ldz + j] = dz;
         }
-    float v = block_sum4(l_part, red, wave, lane);
+    float v = lt_block_sum(l_part, red, wave, lane);
     if (tid == 0) part_loss[blockIdx.x] = v;
-    v = block_sum4(ds_part, red, wave, lane);
+    v = lt_block_sum(ds_part, red, wave, lane);
     if (tid == 0) part_ds[blockIdx.x] = v;
-    v = block_sum4(db_part, red, wave, lane);
+    v = lt_block_sum(db_part, red, wave, lane);
     if (tid == 0) part_db[blockIdx.x] = v;
 }
 

@@ -1,10 +1,6 @@
 """DistillClipLoss without a GPU: the import path and constructor, the flags, create_loss's branch, main's refusals (they
-read only flags and model configs), no CPU fallback, and the kernel source's resource usage for gfx950 (hipcc
-cross-compiles here)."""
+read only flags and model configs), no CPU fallback."""
 import os
-import re
-import subprocess
-import tempfile
 from types import SimpleNamespace
 
 import pytest
@@ -16,7 +12,6 @@ from colxlip_amd.main import distill_refusal
 from colxlip_amd.params import parse_args, unsupported_flag_values
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def test_reference_import_path():
@@ -115,24 +110,3 @@ def test_no_cpu_fallback():
         DistillClipLoss()(fi, ft, torch.tensor(10.0), tfi, tft, torch.tensor(30.0))
     with torch.no_grad(), pytest.raises(RuntimeError, match="device"):
         DistillClipLoss()(fi, ft, torch.tensor(10.0), tfi[:, :48], tft[:, :48], torch.tensor(30.0))
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_kernel_compiles_without_scratch_or_spills():
-    src = os.path.join(ROOT, "colxlip_amd", "csrc", "loss_distill.hip")
-    with tempfile.TemporaryDirectory() as d:
-        cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", src, "-o",
-               os.path.join(d, "ld.s"), "-Rpass-analysis=kernel-resource-usage"]
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    found = 0
-    for m in re.finditer(r"Function Name: (\S+)(.*?)(?=Function Name:|\Z)", r.stderr, re.S):
-        found += 1
-        s = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", m.group(2))
-        assert s is not None and int(s.group(1)) == 0, f"{m.group(1)} uses scratch"
-        for kind in ("VGPRs", "SGPRs"):
-            s = re.search(r"%s Spill: (\d+)" % kind, m.group(2))
-            assert s is None or int(s.group(1)) == 0, f"{m.group(1)} spills {kind}"
-        lds = re.search(r"LDS Size \[bytes/block\]: (\d+)", m.group(2))
-        assert lds is None or int(lds.group(1)) <= 80 * 1024, f"{m.group(1)} uses {lds.group(1)} bytes of LDS"
-    assert found >= 17          # the backward walk for 9 embed dims, forward, merge, the dense and the finishing kernels

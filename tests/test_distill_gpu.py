@@ -140,7 +140,9 @@ def test_large_vs_float64_and_bit_identical():
         assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("es,et", [(64, 128), (48, 96)])
+# every fused dim on the student side (the walk's instantiations) and on the teacher side; (48, 96) takes the dense path
+@pytest.mark.parametrize("es,et", [(64, 128), (16, 1024), (32, 768), (128, 640), (256, 512), (512, 256), (640, 32), (768, 16),
+                                   (1024, 64), (48, 96)])
 @pytest.mark.parametrize("c_mult,off", [(3, 70), (3, 140), (2, 0)])
 def test_nonsquare_local_blocks(es, et, c_mult, off):
     """the local-loss problem: b rows against W*b columns, labels at column r + b*rank"""

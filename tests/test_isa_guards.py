@@ -119,6 +119,39 @@ def test_pipelined_nt_kernel_keeps_its_accumulators(tmp_path):
             assert int(m.group(2)) == 0, f"{m.group(1)} spills {m.group(2)} bytes/lane"
 
 
+_LOSS_WALKS = {"loss_fused.hip": "_Z19ce_fused_bwd_kernel", "loss_sigmoid.hip": "_Z15sig_walk_kernel",
+               "loss_distill.hip": "_Z18distill_bwd_kernel"}
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+@pytest.mark.parametrize("src,min_kernels", [("loss_fused.hip", 13), ("loss_sigmoid.hip", 10), ("loss_distill.hip", 17)])
+def test_kernel_compiles_without_scratch_or_spills(src, min_kernels, tmp_path):
+    """The three fused losses on the tile engine of loss_tile.h: no scratch, no spills, at most 80 KiB of LDS per block, and the
+    backward walks at the waves per SIMD their launch bounds ask for: 2 up to NE = 32 (E = 512), 1 for the AGPR-resident
+    NE = 40, 48, 64 (E = 640, 768, 1024); 3 for the loss-only sigmoid walk (NE = 0)."""
+    _, remarks = _asm(src, tmp_path)
+    found = walks = 0
+    for m in re.finditer(r"Function Name: (\S+)(.*?)(?=Function Name:|\Z)", remarks, re.S):
+        name, body = m.group(1), m.group(2)
+        found += 1
+        s = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", body)
+        assert s is not None and int(s.group(1)) == 0, f"{name} uses scratch"
+        for kind in ("VGPRs", "SGPRs"):
+            s = re.search(r"%s Spill: (\d+)" % kind, body)
+            assert s is None or int(s.group(1)) == 0, f"{name} spills {kind}"
+        lds = re.search(r"LDS Size \[bytes/block\]: (\d+)", body)
+        assert lds is None or int(lds.group(1)) <= 80 * 1024, f"{name} uses {lds.group(1)} bytes of LDS"
+        ne = re.match(r"%sILi(\d+)E" % _LOSS_WALKS[src], name)
+        if ne:
+            walks += 1
+            ne = int(ne.group(1))
+            want = 3 if ne == 0 else (2 if ne <= 32 else 1)
+            occ = int(re.search(r"Occupancy \[waves/SIMD\]: (\d+)", body).group(1))
+            assert occ == want, f"{name}: {occ} waves/SIMD, want {want}"
+    assert found >= min_kernels, found     # the walk for 9 embed dims (+ sigmoid's loss-only walk), forward, merge, sums, dense
+    assert walks == (10 if src == "loss_sigmoid.hip" else 9), walks
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # SGPR written by a VALU instruction, read as an address by a VMEM instruction inside INLINE ASM (round-3 GPU fault).
 _VALU_SGPR_WRITERS = ("v_readlane_b32", "v_readfirstlane_b32")

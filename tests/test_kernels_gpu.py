@@ -967,7 +967,8 @@ def test_l2norm():
 
 
 @pytest.mark.parametrize("np_,nq,E,off,sym", [(50, 50, 64, 0, True), (6, 24, 16, 12, False), (200, 200, 512, 0, True),
-                                              (130, 1000, 32, 300, False), (257, 257, 768, 0, True), (64, 4096, 1024, 1024, False)])
+                                              (130, 1000, 32, 300, False), (257, 257, 768, 0, True), (64, 4096, 1024, 1024, False),
+                                              (100, 100, 128, 0, True), (70, 210, 256, 140, False), (300, 300, 640, 0, True)])
 def test_fused_contrastive_ce(np_, nq, E, off, sym):
     """csrc/loss_fused.hip: loss, both log-sum-exps and every gradient of the contrastive cross-entropy without the logits
     matrix in memory, against plain fp32 PyTorch (reference loss.py:145-152,175-180 arithmetic)."""

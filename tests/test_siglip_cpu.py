@@ -1,10 +1,5 @@
-"""SigLipLoss without a GPU: the flags, create_loss's branch order and refusals, no CPU fallback, and the kernel source's
-resource usage for gfx950 (hipcc cross-compiles here)."""
+"""SigLipLoss without a GPU: the flags, create_loss's branch order and refusals, no CPU fallback."""
 import math
-import os
-import re
-import subprocess
-import tempfile
 from types import SimpleNamespace
 
 import pytest
@@ -14,8 +9,6 @@ from colxlip_amd import SigLipLoss
 from colxlip_amd.factory import create_loss
 from colxlip_amd.params import parse_args, unsupported_flag_values
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def test_reference_import_path():
@@ -73,22 +66,3 @@ def test_no_cpu_fallback():
         SigLipLoss()(fi, ft, torch.tensor(10.0), torch.tensor(-10.0))
     with torch.no_grad(), pytest.raises(RuntimeError, match="device"):
         SigLipLoss()(fi, ft, torch.tensor(math.log(10)), torch.tensor(-10.0))
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_kernel_compiles_without_scratch_or_spills():
-    src = os.path.join(ROOT, "colxlip_amd", "csrc", "loss_sigmoid.hip")
-    with tempfile.TemporaryDirectory() as d:
-        cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", src, "-o",
-               os.path.join(d, "ls.s"), "-Rpass-analysis=kernel-resource-usage"]
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    found = 0
-    for m in re.finditer(r"Function Name: (\S+).*?ScratchSize \[bytes/lane\]: (\d+)", r.stderr, re.S):
-        found += 1
-        assert int(m.group(2)) == 0, f"{m.group(1)} uses {m.group(2)} bytes/lane of scratch"
-    for m in re.finditer(r"Function Name: (\S+)(.*?)(?=Function Name:|\Z)", r.stderr, re.S):
-        for kind in ("VGPRs", "SGPRs"):
-            s = re.search(r"%s Spill: (\d+)" % kind, m.group(2))
-            assert s is None or int(s.group(1)) == 0, f"{m.group(1)} spills {kind}"
-    assert found >= 10          # the walk for 9 embed dims + the loss-only walk, the dense and the finishing kernels

@@ -92,7 +92,7 @@ def test_large_vs_float64():
         assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("e", [64, 48])
+@pytest.mark.parametrize("e", list(ops.FUSED_CE_DIMS) + [48])      # every fused walk instantiation, and the dense path
 @pytest.mark.parametrize("c_mult,pos_off", [(1, -1), (3, 2 * 70), (3, 70)])
 def test_negative_only_and_nonsquare_blocks(e, c_mult, pos_off):
     g = torch.Generator(device=DEV).manual_seed(5)
