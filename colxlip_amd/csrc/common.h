@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include "../../include/clipx.h"
 
 typedef __bf16 bf16_t;
@@ -36,6 +37,25 @@ void clipx_set_error(const char* fmt, ...);
     } while (0)
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// CUs the persistent GEMM grids are sized by: the device's count (256 when HIP cannot say), rounded down to a multiple of 8
+// (blocks are dealt round-robin over the 8 XCDs), at least 8.  honour_switch: the experiment CLIPX_GEMM_CUS=<n>, persistent
+// grids of fewer blocks than CUs, applies.
+static inline int clipx_num_cu(bool honour_switch) {
+    static int cached[2] = {0, 0};
+    int& n_cu = cached[honour_switch ? 1 : 0];
+    if (n_cu == 0) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
+        if (n_cu <= 0) n_cu = 256;
+        n_cu = (n_cu / 8) * 8;
+        if (n_cu < 8) n_cu = 8;
+        const char* e = honour_switch ? getenv("CLIPX_GEMM_CUS") : nullptr;
+        if (e && atoi(e) >= 8 && atoi(e) < n_cu) n_cu = (atoi(e) / 8) * 8;
+    }
+    return n_cu;
+}
 
 // ---- element access: T in {float, bf16_t}; math always in fp32 -----------------------
 template <typename T> __device__ __forceinline__ float to_f(T v) { return (float)v; }

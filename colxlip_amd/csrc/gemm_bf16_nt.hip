@@ -59,12 +59,6 @@ extern "C" int clipx_debug_nt(unsigned long long* out, int reset) {
 #define NT_SLOTS 5                 // ring of operand slots: x(k0) w(k0) x(k1) w(k1) x(k2) ...
 #define NT_SLOT_BYTES (256 * 128)  // one operand (256 rows) of one 64-deep k-step: 32 KiB
 
-// one LDS-DMA piece through a buffer descriptor (a plain __device__ function: inside the kernel's nested generic lambdas the
-// builtin silently suppressed the HOST-side instantiation of the whole kernel template -- undefined stubs at load time)
-__device__ __forceinline__ void nt_dma_piece(__amdgpu_buffer_rsrc_t rsrc, char* lds_dst, unsigned voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LDS_PTR(void))lds_dst, 16, voff, soff, 0, 0);
-}
-
 __device__ __forceinline__ void wait_vmcnt(int n) {
     // n is wave-uniform; s_waitcnt needs an immediate.  A smaller immediate than `n` is always safe.
     if (n >= 36) asm volatile("s_waitcnt vmcnt(36)" ::: "memory");
@@ -197,9 +191,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_kernel(int M, int N, int 
     auto fast_piece = [&](int slot, int i) {        // piece i of the item the load cursor points at
         const int kb = (itl >> 1) * (NT_BK * 2);
         if (itl & 1) {
-            nt_dma_piece(rw, smem + slot * NT_SLOT_BYTES + (4 * wave + i) * 1024, voffw[i], kb);
+            lds_dma_piece(rw, smem + slot * NT_SLOT_BYTES + (4 * wave + i) * 1024, voffw[i], kb);
         } else if (i < XP) {
-            nt_dma_piece(rx, smem + slot * NT_SLOT_BYTES + (XP * wave + i) * 1024, voffx[i < XP ? i : 0], kb);
+            lds_dma_piece(rx, smem + slot * NT_SLOT_BYTES + (XP * wave + i) * 1024, voffx[i < XP ? i : 0], kb);
         }
     };
     auto issue_item = [&](int slot) {
@@ -258,7 +252,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_kernel(int M, int N, int 
     // one k-step: wait for its two items, barrier, refill the two freed slots, multiply.  (The variants of this schedule that were
     // measured and dropped -- second slice held across the barrier, refill pieces between its MFMAs, waves 4-7 half a k-step
     // behind inside one barrier interval -- are in profiles/r02_ablation_tile_order_stores.txt (4); the half-k-step offset that
-    // does pay needs its own ring layout: gemm_bf16_nt8p.hip.)
+    // does pay needs its own ring layout: gemm_nt_pp.h.)
     auto kstep = [&]() {
     #ifdef NT_PROFILE
             long p_a = clock64();
@@ -432,19 +426,7 @@ int launch_gemm_bf16_nt(int M, int N, int K, const bf16_t* X, const bf16_t* W, c
     CLIPX_CHECK(((uintptr_t)X % 16 == 0) && ((uintptr_t)W % 16 == 0) && ((uintptr_t)out % 16 == 0),
                 "bf16 NT GEMM: operands must be 16-B aligned");
     if (M <= 0 || N <= 0) return 0;
-    static int chip_cu = 0;
-    if (chip_cu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            chip_cu = prop.multiProcessorCount;
-        if (chip_cu <= 0) chip_cu = 256;
-        chip_cu = (chip_cu / 8) * 8;
-        if (chip_cu < 8) chip_cu = 8;
-        const char* e = getenv("CLIPX_GEMM_CUS");          // experiment: persistent GEMM grids of fewer blocks than CUs
-        if (e && atoi(e) >= 8 && atoi(e) < chip_cu) chip_cu = (atoi(e) / 8) * 8;
-    }
-    const int n_cu = chip_cu;
+    const int n_cu = clipx_num_cu(true);
     // Tile shape.  The 256x256 tile stages fewest bytes per FLOP (the 128x256 one runs ~0.9x as fast per FLOP).  A
     // partly filled last round of tiles is not worth a smaller tile: the two towers run on separate streams, so the
     // other tower's kernels take the idle CUs (measured at per-GPU batch 512 and 1024: 256x256 everywhere is 4-7 %
@@ -479,32 +461,14 @@ int launch_gemm_bf16_nt(int M, int N, int K, const bf16_t* X, const bf16_t* W, c
         const int rc = launch_gemm_bf16_nt8p(M, N, K, X, W, epi, out, out_dtype, n_cu, stream);
         if (rc != 1) return rc;
     }
-    int fl = 0;
-    if (epi.bias) fl |= F_BIAS;
-    if (epi.residual) fl |= F_RES;
-    if (epi.act_u) fl |= F_ACTU;
-    if (epi.act != CLIPX_ACT_NONE) fl |= F_ACT;
-    if (epi.preact) fl |= F_PRE;
-    if (epi.pre8) fl |= F_PRE8;
-    if (epi.actu8) fl |= F_ACTU8;
-    CLIPX_CHECK(!((fl & F_ACTU) && (fl & F_ACT)), "bf16 NT GEMM: act and act_u are mutually exclusive");
-    const int act = (fl & F_ACTU) ? epi.act_u_kind : ((fl & F_ACT) ? epi.act : CLIPX_ACT_NONE);
+    int fl, act;
+    CLIPX_CHECK(nt_epi_flags(epi, fl, act), "bf16 NT GEMM: act and act_u are mutually exclusive");
 #define NT_CASE(FLV, ACTV) \
     if (fl == (FLV) && act == (ACTV)) return launch_epi<(FLV), (ACTV)>(mt, M, N, K, X, W, epi, out, out_dtype, n_cu, stream)
-    NT_CASE(0, CLIPX_ACT_NONE);                               // dgrad, patch embedding, projections
-    NT_CASE(F_BIAS, CLIPX_ACT_NONE);                          // in_proj
-    NT_CASE(F_BIAS | F_RES, CLIPX_ACT_NONE);                  // out_proj, c_proj (+ residual stream)
-    NT_CASE(F_ACTU, CLIPX_ACT_GELU);                          // c_proj dgrad x GELU'(u)
-    NT_CASE(F_ACTU, CLIPX_ACT_QUICKGELU);
-    NT_CASE(F_BIAS | F_ACT | F_PRE, CLIPX_ACT_GELU);          // c_fc (training: keeps the pre-activation)
-    NT_CASE(F_BIAS | F_ACT | F_PRE, CLIPX_ACT_QUICKGELU);
-    NT_CASE(F_BIAS | F_ACT, CLIPX_ACT_GELU);                  // c_fc (no_grad)
-    NT_CASE(F_BIAS | F_ACT, CLIPX_ACT_QUICKGELU);
+    NT_EPI_CASES(NT_CASE)
     NT_CASE(F_BIAS | F_ACT | F_PRE | F_RES, CLIPX_ACT_GELU);  // everything at once (kernel tests)
     NT_CASE(F_BIAS | F_ACT | F_PRE | F_RES, CLIPX_ACT_QUICKGELU);
     NT_CASE(F_BIAS | F_PRE | F_RES, CLIPX_ACT_NONE);
-    NT_CASE(F_BIAS | F_ACT | F_PRE8, CLIPX_ACT_GELU);         // c_fc (training): GELU' kept on eight bits
-    NT_CASE(F_ACTU8, CLIPX_ACT_NONE);                         // c_proj dgrad x the kept factor
 #undef NT_CASE
     clipx_set_error("bf16 NT GEMM: epilogue combination not built (flags %d, act %d)", fl, act);
     return -1;

@@ -18,6 +18,7 @@
 //     n of one m; lane l and l+32 hold adjacent runs), operands read in that store layout and un-swapped.
 #include <stdlib.h>
 #include "gemm_epi.h"
+#include "gemm_nt_epilogue.h"
 
 static __device__ __attribute__((aligned(64))) unsigned char g_zero_page[64];
 #ifdef NT_PROFILE
@@ -669,14 +670,8 @@ int launch_gemm_bf16_nt5(int M, int N, int K, const bf16_t* X, const bf16_t* W, 
                          hipStream_t stream) {
     if (M % N5_BM != 0 || N % N5_BN != 0 || K % N5_BK != 0) return 1;
     if (epi.pre8 || epi.actu8 || epi.ms_max) return 1;     // epilogues this kernel does not build
-    int fl = 0;
-    if (epi.bias) fl |= F_BIAS;
-    if (epi.residual) fl |= F_RES;
-    if (epi.act_u) fl |= F_ACTU;
-    if (epi.act != CLIPX_ACT_NONE) fl |= F_ACT;
-    if (epi.preact) fl |= F_PRE;
-    if ((fl & F_ACTU) && (fl & F_ACT)) return 1;
-    const int act = (fl & F_ACTU) ? epi.act_u_kind : ((fl & F_ACT) ? epi.act : CLIPX_ACT_NONE);
+    int fl, act;
+    if (!nt_epi_flags(epi, fl, act)) return 1;
     const int nk = K / N5_BK;
 #define N5_CASE(FLV, ACTV) \
     if (fl == (FLV) && act == (ACTV)) return launch_one<(FLV), (ACTV), 0>(M, N, K, X, W, epi, out, n_cu, stream)

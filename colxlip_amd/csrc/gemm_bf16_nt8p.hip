@@ -1,47 +1,40 @@
 // Eight-wave PING-PONG bf16 NT GEMM:  y[M,N] = epi(x[M,K] . w[N,K]^T), 256x256 tile, K % 64 == 0.
 //
-// Same tile, same MFMA (v_mfma_f32_16x16x32_bf16), same LDS image, same loader instruction and the same epilogue as
-// gemm_bf16_nt.hip; what differs is WHEN the two waves of a SIMD do what.  There both waves of a SIMD (w and w + 4) leave a
-// barrier together, read their fragments together, issue their LDS-DMA pieces together and then compete for the one matrix
-// pipe: a 64-deep k-step costs ~3500-3900 cycles against 2048 cycles of MFMA issue.  Here a wave's k-step is two segments
-// separated by barriers,
-//     L: 24 fragment reads (the whole k-step: 96 VGPRs) + 8 LDS-DMA pieces        C: 64 MFMAs, nothing else
-// and waves 4-7 run ONE SEGMENT BEHIND waves 0-3 (one extra barrier before their loop, one extra after the others'), so on
-// every SIMD one wave is in C while its partner is in L: the matrix pipe sees one uninterrupted MFMA stream, and the loads /
-// reads / waits of the partner happen beside it instead of before it.
-//
-// Interval 2j: group A (waves 0-3) in L_j, group B (waves 4-7) in C_{j-1};  interval 2j+1: A in C_j, B in L_j.
-//
-// Tile split between the groups: A owns tile columns 0..127, B columns 128..255 (each wave 128 rows x 64 columns), so the x
-// rows of a k-step are SHARED and each group's 128 w rows are PRIVATE to it.  LDS (160 KiB):
-//     X  ring: 3 slots x 32 KiB (256 rows x 64 k)      W_A ring: 2 x 16 KiB      W_B ring: 2 x 16 KiB
-// A slot may be refilled only after a barrier that follows its last read, and a piece must have landed -- seen by its
-// issuing wave's vmcnt wait -- before a barrier that precedes its first read.  The assignment that keeps every piece at
-// least two intervals in flight, with 8 pieces per wave and k-step:
-//     A in L_j issues   W_B(j+1) [4 pieces/wave]  then its half of X(j+2) [4]
-//     B in L_j issues   W_A(j+2) [4]              then its half of X(j+2) [4]
-// and the waits sit at the END of the C segment, in front of its barrier (at the end of L they were measured 2.5 % slower: the L
-// side of an interval is the longer one):
-//     A, end of C_j (interval 2j+1):  s_waitcnt vmcnt(4) -- everything but its X(j+2) pieces has landed: W_B(j+1), which B reads
-//        after barrier 2j+3, and its half of X(j+1), which everyone reads after barrier 2j+2
-//     B, end of C_j (interval 2j+2):  s_waitcnt vmcnt(0) -- W_A(j+2) and its half of X(j+2), both read after barrier 2j+4
-// (A's X(j+2) half is covered by A's next wait, in front of barrier 2j+4.)  Freed slots: X(j-1) was last read in interval 2j-1,
-// W_B(j-1) in 2j-1, W_A(j) in 2j -- all before the barrier that precedes the segment overwriting them.  Each group stages the
-// OTHER group's w rows: a slot a group reads is then never written in the same interval by a wave that cannot know its
-// neighbours' reads are done.
-// Tile end: group A runs the epilogue after the barrier that follows its last C segment, group B before it -- both epilogues
-// then fall into the same interval (A: epilogue + L_0 of the next tile; B: last C + epilogue).
-#include <stdlib.h>
-#include <type_traits>
-#include "kernels.h"
-#include "gemm_epi.h"
+// The schedule, its hazard argument, the tile walk and the launch geometry are the engine's (gemm_nt_pp.h).  This file supplies
+// what is bf16 about it: a k-step is 64 elements, a C segment is 2 x 32 v_mfma_f32_16x16x32_bf16 (the MFMA of gemm_bf16_nt.hip),
+// and a tile ends in that kernel's epilogue (gemm_nt_epilogue.h) or in the MaxSim reduction (gemm_nt_maxsim.h).
+#include "gemm_nt_pp.h"
 #include "gemm_nt_epilogue.h"
 #include "gemm_nt_maxsim.h"
 
-#define PP_X_BYTES (256 * 128)      // 32 KiB: 256 x rows of one 64-deep k-step
-#define PP_W_BYTES (128 * 128)      // 16 KiB: one group's 128 w rows
-#define PP_W_BASE (3 * PP_X_BYTES)  // W_A ring at 96 KiB, W_B ring at 128 KiB
-#define PP_LDS (3 * PP_X_BYTES + 4 * PP_W_BYTES)
+struct PpBf16 {
+    typedef bf16_t elem;
+    typedef bf16x8 frag;
+    // slice ks of a k-step is k 32 ks .. 32 ks + 31; lane group g holds k 8 g .. 8 g + 7 of it
+    static __device__ __forceinline__ int chunk(int ks, int g) { return ks * 4 + g; }
+    // fragments of slice s: F[12 s + i] = w-tile i (i < 4), F[12 s + 4 + j] = x-tile j
+    template <bool FIRST>
+    static __device__ __forceinline__ void mfma(f32x4 (&acc)[4][8], frag (&F)[24]) {
+        static_for<0, 8>([&](auto jc) {
+            constexpr int j_ = decltype(jc)::value;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if constexpr (FIRST)
+                    acc[i][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(F[i], F[4 + j_], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                else
+                    acc[i][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(F[i], F[4 + j_], acc[i][j_], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        static_for<0, 8>([&](auto jc) {
+            constexpr int j_ = decltype(jc)::value;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                acc[i][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(F[12 + i], F[12 + 4 + j_], acc[i][j_], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        });
+    }
+};
 
 #ifdef PP_PROFILE
 // per wave: [0] total [1] epilogue [2] L segment [3] wait before the post-L barrier .. [4] C segment [5] vmcnt wait [6] barrier
@@ -54,320 +47,50 @@ extern "C" int clipx_debug_nt8p(unsigned long long* out, int reset) {
     }
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pp_dbg), 64 * sizeof(unsigned long long));
 }
+struct PpProbe {
+    long t0 = clock64(), last = 0, sum[8] = {0, 0, 0, 0, 0, 0, 0, 1};
+    __device__ __forceinline__ void tick() { last = clock64(); }
+    template <int I>
+    __device__ __forceinline__ void lap() {
+        const long t = clock64();
+        sum[I] += t - last;
+        last = t;
+        if constexpr (I == PP_T_VMCNT) ++sum[7];      // one counted wait per k-step
+    }
+    __device__ __forceinline__ void flush(int wave, int lane) {
+        sum[0] = clock64() - t0;
+        if (lane == 0)
+            for (int i = 0; i < 8; ++i) atomicAdd(&g_pp_dbg[wave * 8 + i], (unsigned long long)sum[i]);
+    }
+};
+#else
+typedef PpNoProbe PpProbe;
 #endif
 
-__device__ __forceinline__ void pp_dma_piece(__amdgpu_buffer_rsrc_t rsrc, char* lds_dst, unsigned voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LDS_PTR(void))lds_dst, 16, voff, soff, 0, 0);
-}
-
-#ifndef PP_READS_FIRST
-#define PP_READS_FIRST 12     // fragment reads issued before the segment's first LDS-DMA piece (the rest follow the w pieces)
-#endif
-// n is wave-uniform; s_waitcnt needs an immediate, and a smaller immediate than n is always safe
-__device__ __forceinline__ void pp_wait_vmcnt(int n) {
-    if (n >= 40) asm volatile("s_waitcnt vmcnt(40)" ::: "memory");
-    else if (n >= 36) asm volatile("s_waitcnt vmcnt(36)" ::: "memory");
-    else if (n >= 24) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-    else if (n >= 20) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-    else if (n >= 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else if (n >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (n >= 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if (n >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if (n >= 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-// fragment f of a k-step: slice s = f / 12; r = f % 12: w-tile r (r < 4) or x-tile r - 4; tiles are 2 KiB apart
-template <int f>
-__device__ __forceinline__ void pp_frag_read(bf16x8& dst, const unsigned (&wa)[2], const unsigned (&xa)[2]) {
-    constexpr int s = f / 12, r = f % 12;
-    if constexpr (r < 4)
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(wa[s]), "n"(r * 2048));
-    else
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(xa[s]), "n"((r - 4) * 2048));
-}
-
-// Tile walk.  Blocks are dealt to the 8 XCDs round-robin (block b -> XCD b & 7, its rank there b >> 3), and every XCD walks ITS
-// OWN m-panels (tm = xcd, xcd + 8, ...) gm panels x all n-tiles at a time, n-tile by n-tile, so the x panel of a tile and the
-// weight tiles of a walk block stay in that XCD's L2.  The XCD's tiles are dealt to its blocks round-robin; the last round may
-// be partly empty.  (A split-K tail for that round -- its tiles split along K over the idle blocks, fp32 partial tiles folded
-// by the last arrival -- was built in round 2 and measured SLOWER wherever it triggered, profiles/r02_ablation_pingpong.txt (8):
-// NT layer-pair sum 8.55 -> 8.65 ms, per-GPU batch 512 step 24.5 -> 25.5 ms; removed in round 4.)
 template <typename OUT_T, int FL, int ACT>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_nt8p_kernel(int M, int N, int K, const bf16_t* __restrict__ X,
                                                                 const bf16_t* __restrict__ W, EpiB16 epi,
                                                                 OUT_T* __restrict__ out, int tiles_m, int tiles_n, int gm) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int MT = 8, FS = 12, NF = 24;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int g = lane >> 4, c = lane & 15;
-    const int grp = wave >> 2, wq = wave & 3;       // group A / B; wave within the group
-    const int wm = wq >> 1, wn = 2 * grp + (wq & 1);
-    const int nk = K / 64;
-
-    // ---- this block's work items
-    const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3, cpx = gridDim.x >> 3;
-    const int P = (tiles_m - xcd + 7) >> 3;                 // m-panels of this XCD
-    const int n_x = P * tiles_n;
-    const int per = gm * tiles_n;
-    auto tile_of = [&](int l, int& tm, int& tn) {           // l-th tile of the XCD's walk
-        const int blk = l / per, r = l - blk * per;
-        const int gmb = min(gm, P - blk * gm);
-        tn = r / gmb;
-        tm = ((blk * gm + (r - tn * gmb)) << 3) + xcd;
-    };
-    const int nitems = jb < n_x ? (n_x - jb + cpx - 1) / cpx : 0;
-    if (nitems == 0) return;
-    auto item_tile = [&](int idx) { return jb + cpx * idx; };
-    auto item_k0 = [&](int) { return 0; };
-    auto item_k1 = [&](int) { return nk; };
-
-    // ---- load side.  One piece = 1 KiB = 8 rows x 128 B; lane -> row l>>3, 16-byte slot l&7 holding chunk (l&7)^(row&7).
-    const int srow = lane >> 3, lchunk = (lane & 7) ^ srow;
-    // ONE per-lane byte offset per operand (piece 0 of this wave); pieces 1..3 are 8, 16, 24 rows further, which goes into the
-    // scalar offset of the load together with the k-step
-    const unsigned voffx = (unsigned)(((4 * wave) * 8 + srow) * K + lchunk * 8) * 2u;     // x pieces 4*wave .. 4*wave+3 of 32
-    const unsigned voffw = (unsigned)(((4 * wq) * 8 + srow) * K + lchunk * 8) * 2u;       // pieces 4*wq .. of the OTHER group's 16
-    const int piece_stride = 16 * K;                                                       // 8 rows, in bytes
-    const int og = grp ^ 1;
-    // two cursors through the same item sequence: x (k-step j+2) and the other group's w (A: j+1, B: j+2)
-    int ix = 0, kx = item_k0(0), kx1 = item_k1(0), iw = 0, kw = kx, kw1 = kx1;
-    __amdgpu_buffer_rsrc_t rx, rw;
-    auto set_x_tile = [&](int idx) {
-        int tm, tn;
-        tile_of(item_tile(idx), tm, tn);
-        const int m0 = tm * 256;
-        const int xr = min(256, M - m0);
-        rx = __builtin_amdgcn_make_buffer_rsrc((void*)(X + (long)m0 * K), 0, xr * K * 2, 0x00020000);
-    };
-    auto set_w_tile = [&](int idx) {
-        int tm, tn;
-        tile_of(item_tile(idx), tm, tn);
-        const int n0 = tn * 256 + og * 128;
-        // (clamping both ways selects v_med3_i32, a VALU result: the descriptor then sits in VGPRs and every piece becomes a
-        // readfirstlane waterfall loop)
-        const int wr = __builtin_amdgcn_readfirstlane(max(0, min(128, N - n0)));
-        rw = __builtin_amdgcn_make_buffer_rsrc((void*)(W + (long)min(n0, N - 1) * K), 0, wr * K * 2, 0x00020000);
-    };
-    int xls = 0, wls = 0;      // slots the cursors write next
-    auto issue_x = [&]() -> bool {      // this wave's 4 pieces of the x item at the cursor
-        if (ix >= nitems) return false;
-        char* dst = smem + xls * PP_X_BYTES + (4 * wave) * 1024;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) pp_dma_piece(rx, dst + i * 1024, voffx, kx * 128 + i * piece_stride);
-        xls = (xls == 2) ? 0 : xls + 1;
-        if (++kx == kx1) {
-            if (++ix < nitems) {
-                kx = item_k0(ix);
-                kx1 = item_k1(ix);
-                set_x_tile(ix);
-            }
-        }
-        return true;
-    };
-    auto issue_w = [&]() -> bool {      // this wave's 4 pieces of the OTHER group's w sub-item at the cursor
-        if (iw >= nitems) return false;
-        char* dst = smem + PP_W_BASE + og * (2 * PP_W_BYTES) + wls * PP_W_BYTES + (4 * wq) * 1024;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) pp_dma_piece(rw, dst + i * 1024, voffw, kw * 128 + i * piece_stride);
-        wls ^= 1;
-        if (++kw == kw1) {
-            if (++iw < nitems) {
-                kw = item_k0(iw);
-                kw1 = item_k1(iw);
-                set_w_tile(iw);
-            }
-        }
-        return true;
-    };
-
-    set_x_tile(0);
-    set_w_tile(0);
-    // prologue = the issues of the "virtual" segments L_-2, L_-1:  A: X(0) | W_B(0), X(1);   B: W_A(0), X(0) | W_A(1), X(1)
-    if (grp == 0) {
-        issue_x();
-        issue_w();
-        issue_x();
-    } else {
-        issue_w();
-        issue_x();
-        issue_w();
-        issue_x();
-    }
-    // everything of k-step 0 (and, for B, of k-step 1: its first wait inside the loop comes too late for A's L_1) has landed
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (grp == 1) __builtin_amdgcn_s_barrier();     // B runs one segment behind
-
-    f32x4 acc[4][MT];
-    bf16x8 F[NF];
-    const int sw = c & 7;
-    const unsigned lds0 = (unsigned)(size_t)smem;
-    const unsigned xoff = lds0 + (wm * 128 + c) * 128;
-    const unsigned woff = lds0 + PP_W_BASE + grp * (2 * PP_W_BYTES) + ((wq & 1) * 64 + c) * 128;
-    unsigned coff[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) coff[ks] = ((ks * 4 + g) ^ sw) * 16;
-
-#ifdef PP_PROFILE
-    long p_t0 = clock64(), p_epi = 0, p_l = 0, p_lw = 0, p_c = 0, p_vm = 0, p_cb = 0, p_n = 1;
-#endif
-    int ic = 0, kc = item_k0(0), kc1 = item_k1(0), xrs = 0, wrs = 0;
-    // One k-step: L segment, barrier, C segment, the counted wait.  FIRST (the first k-step of an item) starts the accumulators
-    // from zero inside the MFMAs.  Two instantiations, called from a loop that is peeled by hand: with a run-time flag selecting
-    // the two MFMA forms inside ONE loop body the register allocator joins 128 accumulators from both and spills ~200 VGPRs.
-    auto kstep = [&](auto first_c) {
-        constexpr bool FIRST = decltype(first_c)::value;
-        // ------------------------------------------------ L segment
-#ifdef PP_PROFILE
-        long t0 = clock64();
-#endif
-        int issued = 0;
-        {
-            unsigned wa[2], xa[2];
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                wa[ks] = woff + wrs * PP_W_BYTES + coff[ks];
-                xa[ks] = xoff + xrs * PP_X_BYTES + coff[ks];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            static_for<0, PP_READS_FIRST>([&](auto fc) { pp_frag_read<decltype(fc)::value>(F[decltype(fc)::value], wa, xa); });
-            __builtin_amdgcn_sched_barrier(0);
-            if (issue_w()) issued += 4;
-            __builtin_amdgcn_sched_barrier(0);
-            static_for<PP_READS_FIRST, 24>([&](auto fc) { pp_frag_read<decltype(fc)::value>(F[decltype(fc)::value], wa, xa); });
-            __builtin_amdgcn_sched_barrier(0);
-            if (issue_x()) issued += 4;
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#ifdef PP_PROFILE
-        long t1 = clock64();
-#endif
-        // all 24 fragments in registers before the barrier: the slots may be refilled right after it
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(F[0]), "+v"(F[1]), "+v"(F[2]), "+v"(F[3]), "+v"(F[4]), "+v"(F[5]), "+v"(F[6]), "+v"(F[7]), "+v"(F[8]),
-                       "+v"(F[9]), "+v"(F[10]), "+v"(F[11]), "+v"(F[12]), "+v"(F[13]), "+v"(F[14]), "+v"(F[15]), "+v"(F[16]),
-                       "+v"(F[17]), "+v"(F[18]), "+v"(F[19]), "+v"(F[20]), "+v"(F[21]), "+v"(F[22]), "+v"(F[23]));
-        __builtin_amdgcn_s_barrier();
-#ifdef PP_PROFILE
-        long t2 = clock64();
-#endif
-        // ------------------------------------------------ C segment
-        __builtin_amdgcn_sched_barrier(0);
-        static_for<0, MT>([&](auto jc) {
-            constexpr int j_ = decltype(jc)::value;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if constexpr (FIRST)
-                    acc[i][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(F[i], F[4 + j_], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                else
-                    acc[i][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(F[i], F[4 + j_], acc[i][j_], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        });
-        static_for<0, MT>([&](auto jc) {
-            constexpr int j_ = decltype(jc)::value;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                acc[i][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(F[FS + i], F[FS + 4 + j_], acc[i][j_], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        });
-#ifdef PP_PROFILE
-        long t3 = clock64();
-#endif
-        // what the readers after the coming barrier(s) need from this wave has landed: A leaves its x pieces (needed two barriers
-        // later, waited for at the end of its next C segment) in flight, B nothing.  (Before a tile's epilogue, so that no store
-        // is waited for.)
-        if (grp == 0 && issued == 8) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef PP_PROFILE
-        long t3b = clock64();
-        p_l += t1 - t0; p_lw += t2 - t1; p_c += t3 - t2; p_vm += t3b - t3; ++p_n;
-#endif
-        xrs = (xrs == 2) ? 0 : xrs + 1;
-        wrs ^= 1;
-    };
-    while (true) {
-        kstep(std::true_type{});
-        while (++kc != kc1) {
-#ifdef PP_PROFILE
-            long tb = clock64();
-#endif
-            __builtin_amdgcn_s_barrier();
-#ifdef PP_PROFILE
-            p_cb += clock64() - tb;
-#endif
-            kstep(std::false_type{});
-        }
-        // ---------------- end of an item.  Group A runs the epilogue AFTER the barrier that ends this interval, group B BEFORE it:
-        // both then sit in the same interval (A: epilogue + L_0 of the next tile; B: its last C segment + epilogue) instead of
-        // each group idling through the other's.  One call site, so one copy of the epilogue code.
-        if (grp == 0) __builtin_amdgcn_s_barrier();
-#ifdef PP_PROFILE
-        long te0 = clock64();
-#endif
-        int tm, tn;
-        tile_of(item_tile(ic), tm, tn);
-        if constexpr ((FL & F_MAXSIM) != 0)
-            nt_maxsim_epilogue<MT>(acc, epi, M, N, tm * 256, tn * 256, wm, wn, lane);
-        else
-            (void)nt_tile_epilogue<OUT_T, MT, FL, ACT>(acc, epi, out, M, N, tm * 256, tn * 256, wm, wn, lane);
-#ifdef PP_PROFILE
-        p_epi += clock64() - te0;
-#endif
-        if (grp == 1) __builtin_amdgcn_s_barrier();
-        if (++ic >= nitems) break;
-        kc = item_k0(ic);
-        kc1 = item_k1(ic);
-    }
-    if (grp == 0) __builtin_amdgcn_s_barrier();     // the barrier that ends B's last C segment
-#ifdef PP_PROFILE
-    if (lane == 0) {
-        unsigned long long* d = g_pp_dbg + wave * 8;
-        atomicAdd(&d[0], (unsigned long long)(clock64() - p_t0));
-        atomicAdd(&d[1], (unsigned long long)p_epi);
-        atomicAdd(&d[2], (unsigned long long)p_l);
-        atomicAdd(&d[3], (unsigned long long)p_lw);
-        atomicAdd(&d[4], (unsigned long long)p_c);
-        atomicAdd(&d[5], (unsigned long long)p_vm);
-        atomicAdd(&d[6], (unsigned long long)p_cb);
-        atomicAdd(&d[7], (unsigned long long)p_n);
-    }
-#endif
+    pp_gemm_nt<PpBf16>(M, N, K, X, W, tiles_m, tiles_n, gm,
+                       [&](f32x4 (&acc)[4][8], int m0, int n0, int wm, int wn, int lane) {
+                           if constexpr ((FL & F_MAXSIM) != 0)
+                               nt_maxsim_epilogue<8>(acc, epi, M, N, m0, n0, wm, wn, lane);
+                           else
+                               (void)nt_tile_epilogue<OUT_T, 8, FL, ACT>(acc, epi, out, M, N, m0, n0, wm, wn, lane);
+                       },
+                       PpProbe());
 }
 
-template <typename OUT_T, int FL, int ACT>
-static int launch_pp(int M, int N, int K, const bf16_t* X, const bf16_t* W, const EpiB16& epi, OUT_T* out, int n_cu,
+template <int FL, int ACT>
+static int launch_pp(int M, int N, int K, const bf16_t* X, const bf16_t* W, const EpiB16& epi, bf16_t* out, int n_cu,
                      hipStream_t stream) {
-    const int tiles_m = cdiv(M, 256), tiles_n = cdiv(N, 256);
-    const int gm = nt_pick_gm(N, K, tiles_m);
-    // one block per CU; fewer when XCD 0 (which has the most m-panels) has fewer tiles than CUs
-    const int per_xcd = ((tiles_m + 7) >> 3) * tiles_n;
-    const int grid = per_xcd * 8 < n_cu ? per_xcd * 8 : n_cu;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)gemm_bf16_nt8p_kernel<OUT_T, FL, ACT>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)PP_LDS);
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((gemm_bf16_nt8p_kernel<OUT_T, FL, ACT>), dim3(grid), dim3(512), PP_LDS, stream, M, N, K, X, W, epi, out,
-                       tiles_m, tiles_n, gm);
-    CLIPX_LAUNCH_CHECK();
-    return 0;
+    return pp_launch<gemm_bf16_nt8p_kernel<bf16_t, FL, ACT>>(M, N, K, X, W, epi, out, n_cu, stream);
 }
 
 // S = X . W^T reduced on the fly to per-(row, slot, segment) maxima (gemm_nt_maxsim.h); nothing else is written
 int launch_gemm_bf16_nt8p_maxsim(int M, int N, int K, const bf16_t* X, const bf16_t* W, const EpiB16& epi, hipStream_t stream) {
     if (K % 64 != 0 || K < 128 || (long)256 * K * 2 >= (1l << 31) || epi.ms_q < 64 || epi.ms_q > 65535) return 1;
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount >= 8)
-                   ? (prop.multiProcessorCount / 8) * 8 : 256;
-    }
-    return launch_pp<bf16_t, F_MAXSIM, CLIPX_ACT_NONE>(M, N, K, X, W, epi, (bf16_t*)nullptr, n_cu, stream);
+    return launch_pp<F_MAXSIM, CLIPX_ACT_NONE>(M, N, K, X, W, epi, nullptr, clipx_num_cu(false), stream);
 }
 
 // 1 = this kernel does not apply (the caller falls back to the one-barrier kernel)
@@ -375,29 +98,11 @@ int launch_gemm_bf16_nt8p(int M, int N, int K, const bf16_t* X, const bf16_t* W,
                           int n_cu, hipStream_t stream) {
     if (K % 64 != 0 || K < 128 || out_dtype != CLIPX_BF16) return 1;
     if ((long)256 * K * 2 >= (1l << 31)) return 1;
-    int fl = 0;
-    if (epi.bias) fl |= F_BIAS;
-    if (epi.residual) fl |= F_RES;
-    if (epi.act_u) fl |= F_ACTU;
-    if (epi.act != CLIPX_ACT_NONE) fl |= F_ACT;
-    if (epi.preact) fl |= F_PRE;
-    if (epi.pre8) fl |= F_PRE8;
-    if (epi.actu8) fl |= F_ACTU8;
-    if ((fl & F_ACTU) && (fl & F_ACT)) return 1;
-    const int act = (fl & F_ACTU) ? epi.act_u_kind : ((fl & F_ACT) ? epi.act : CLIPX_ACT_NONE);
+    int fl, act;
+    if (!nt_epi_flags(epi, fl, act)) return 1;
 #define PP_CASE(FLV, ACTV) \
-    if (fl == (FLV) && act == (ACTV)) return launch_pp<bf16_t, (FLV), (ACTV)>(M, N, K, X, W, epi, (bf16_t*)out, n_cu, stream)
-    PP_CASE(0, CLIPX_ACT_NONE);
-    PP_CASE(F_BIAS, CLIPX_ACT_NONE);
-    PP_CASE(F_BIAS | F_RES, CLIPX_ACT_NONE);
-    PP_CASE(F_ACTU, CLIPX_ACT_GELU);
-    PP_CASE(F_ACTU, CLIPX_ACT_QUICKGELU);
-    PP_CASE(F_BIAS | F_ACT | F_PRE, CLIPX_ACT_GELU);
-    PP_CASE(F_BIAS | F_ACT | F_PRE, CLIPX_ACT_QUICKGELU);
-    PP_CASE(F_BIAS | F_ACT, CLIPX_ACT_GELU);
-    PP_CASE(F_BIAS | F_ACT, CLIPX_ACT_QUICKGELU);
-    PP_CASE(F_BIAS | F_ACT | F_PRE8, CLIPX_ACT_GELU);         // c_fc (training): GELU' kept on eight bits (gemm_epi.h)
-    PP_CASE(F_ACTU8, CLIPX_ACT_NONE);                         // c_proj dgrad x the kept factor
+    if (fl == (FLV) && act == (ACTV)) return launch_pp<(FLV), (ACTV)>(M, N, K, X, W, epi, (bf16_t*)out, n_cu, stream)
+    NT_EPI_CASES(PP_CASE)
 #undef PP_CASE
     return 1;
 }

@@ -31,10 +31,6 @@ static __device__ __attribute__((aligned(64))) unsigned char g_zero_page[64];
 #ifndef TN_FAST_LOADER
 #define TN_FAST_LOADER 1   // buffer-descriptor LDS-DMA addressing when N and K are multiples of 256 (every production shape)
 #endif
-// one LDS-DMA piece through a buffer descriptor (kept in a plain __device__ function, see gemm_bf16_nt.hip)
-__device__ __forceinline__ void tn_dma_piece(__amdgpu_buffer_rsrc_t rsrc, char* lds_dst, unsigned voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LDS_PTR(void))lds_dst, 16, voff, soff, 0, 0);
-}
 
 __device__ __forceinline__ void tn_wait_vmcnt(int n) {
     if (n >= 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
@@ -113,11 +109,11 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_kernel(int M, int N, int 
             if (it_next & 1) {
                 const int so = step * (TN_BM * 2) * K;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) tn_dma_piece(rxx, base + (4 * wave + i) * 1024, voff_x[i], so);
+                for (int i = 0; i < 4; ++i) lds_dma_piece(rxx, base + (4 * wave + i) * 1024, voff_x[i], so);
             } else {
                 const int so = step * (TN_BM * 2) * N;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) tn_dma_piece(rdy, base + (4 * wave + i) * 1024, voff_dy[i], so);
+                for (int i = 0; i < 4; ++i) lds_dma_piece(rdy, base + (4 * wave + i) * 1024, voff_dy[i], so);
             }
             ++it_next;
             return;
@@ -276,7 +272,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_kernel(int M, int N, int 
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// PING-PONG form of the same kernel (see gemm_bf16_nt8p.hip for the scheme and its hazard analysis): a step is an L segment
+// PING-PONG form of the same kernel (see gemm_nt_pp.h for the scheme and its hazard analysis): a step is an L segment
 // (48 transposed fragment reads + 8 LDS-DMA pieces) and a C segment (64 MFMAs) with a barrier after each, and waves 4-7 run one
 // segment behind waves 0-3, so on every SIMD one wave multiplies while its partner loads.  Groups split the tile by x columns
 // (wk = wave >> 2, as before): the dy rows of a step are SHARED (3 slots x 32 KiB), each group's 128-column half of the x rows
@@ -355,7 +351,7 @@ __device__ __forceinline__ void tn_pp_body(int M, int N, int K, const bf16_t* __
         char* dst = smem + yls * TNP_DY_BYTES + (4 * wave) * 1024;
         const int so = sy * (TN_BM * 2) * N;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) tn_dma_piece(rdy, dst + i * 1024, voff_dy0 ^ (unsigned)(i << 4), so + i * 8 * N);
+        for (int i = 0; i < 4; ++i) lds_dma_piece(rdy, dst + i * 1024, voff_dy0 ^ (unsigned)(i << 4), so + i * 8 * N);
         yls = (yls == 2) ? 0 : yls + 1;
         ++sy;
         return true;
@@ -365,7 +361,7 @@ __device__ __forceinline__ void tn_pp_body(int M, int N, int K, const bf16_t* __
         char* dst = smem + TNP_X_BASE + og * (2 * TNP_X_BYTES) + xls * TNP_X_BYTES + (4 * wn) * 1024;
         const int so = sx * (TN_BM * 2) * K;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) tn_dma_piece(rxx, dst + i * 1024, voff_x0 ^ (unsigned)(i << 4), so + i * 8 * K);
+        for (int i = 0; i < 4; ++i) lds_dma_piece(rxx, dst + i * 1024, voff_x0 ^ (unsigned)(i << 4), so + i * 8 * K);
         xls ^= 1;
         ++sx;
         return true;
@@ -654,19 +650,7 @@ extern "C" int clipx_select_tn_pp(int which) {
     return 0;
 }
 
-static int tn_num_cu() {
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            n_cu = prop.multiProcessorCount;
-        if (n_cu <= 0) n_cu = 256;
-        const char* e = getenv("CLIPX_GEMM_CUS");          // experiment: persistent GEMM grids of fewer blocks than CUs
-        if (e && atoi(e) >= 8 && atoi(e) < n_cu) n_cu = (atoi(e) / 8) * 8;
-    }
-    return n_cu;
-}
+static int tn_num_cu() { return clipx_num_cu(true); }
 
 // workspace layout: [colsum partials: max(#CU, tiles) x N floats][split slabs]
 static size_t tn_cs_reserve(int N, int K) {

@@ -3,38 +3,40 @@
 // x8 / w8: e4m3 bytes with one power-of-two exponent per row (activations: clipx_quant_rows_e4m3; weights:
 // clipx_quant_weight_e4m3), products and sums exact / fp32 in the MFMA.  BASELINE.json config 5 ("fp8 weights, CDNA4 fp8 MFMA").
 //
-// The kernel is the eight-wave ping-pong kernel of gemm_bf16_nt8p.hip with one substitution: a k-step is 128 fp8 elements, i.e.
-// the SAME 128-byte rows, LDS image, rings, LDS-DMA pieces, hazard argument and tile walk (see that file's header), and a lane's
-// MFMA operand is 32 consecutive k of one row = the two 16-byte chunks 2g, 2g+1 of the row (two ds_read_b128 into one 8-VGPR
-// tuple).  A C segment is 32 MFMAs of 32 cycles: the same 1024 cycles as 64 bf16 MFMAs, for twice the K.
-#include <stdlib.h>
-#include <type_traits>
-#include "kernels.h"
-#include "gemm_epi.h"
+// The kernel is an instance of the eight-wave ping-pong engine (gemm_nt_pp.h: schedule, hazard argument, tile walk, launch
+// geometry), as gemm_bf16_nt8p.hip is.  What is fp8 about it: a k-step is 128 elements, i.e. the SAME 128-byte rows, LDS image,
+// rings and LDS-DMA pieces; a lane's MFMA operand is 32 consecutive k of one row = the two 16-byte chunks 2g, 2g+1 of the row (two
+// ds_read_b128 into one 8-VGPR tuple), so a C segment is 32 MFMAs of 32 cycles: the same 1024 cycles as 64 bf16 MFMAs, for
+// twice the K; and the row exponents are applied to the accumulators before the tile epilogue.
+#include "gemm_nt_pp.h"
 #include "gemm_nt_epilogue.h"
-
-#define PP_X_BYTES (256 * 128)      // 32 KiB: 256 x rows of one 128-deep k-step
-#define PP_W_BYTES (128 * 128)      // 16 KiB: one group's 128 w rows
-#define PP_W_BASE (3 * PP_X_BYTES)  // W_A ring at 96 KiB, W_B ring at 128 KiB
-#define PP_LDS (3 * PP_X_BYTES + 4 * PP_W_BYTES)
-#define PP_READS_FIRST 12
 
 typedef __attribute__((ext_vector_type(4))) int f8x16;      // 16 fp8 bytes
 typedef __attribute__((ext_vector_type(8))) int f8x32;      // one lane's MFMA operand: 32 fp8 bytes
 
-__device__ __forceinline__ void f8_dma_piece(__amdgpu_buffer_rsrc_t rsrc, char* lds_dst, unsigned voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LDS_PTR(void))lds_dst, 16, voff, soff, 0, 0);
-}
-
-// fragment f of a k-step: half h = f / 12 (k 0..15 / 16..31 of the lane's 32); r = f % 12: w-tile r (r < 4) or x-tile r - 4
-template <int f>
-__device__ __forceinline__ void f8_frag_read(f8x16& dst, const unsigned (&wa)[2], const unsigned (&xa)[2]) {
-    constexpr int s = f / 12, r = f % 12;
-    if constexpr (r < 4)
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(wa[s]), "n"(r * 2048));
-    else
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(xa[s]), "n"((r - 4) * 2048));
-}
+struct PpFp8 {
+    typedef unsigned char elem;
+    typedef f8x16 frag;
+    // half ks (k 0..15 / 16..31 of the lane's 32) of lane group g: chunks 2g, 2g+1 = k 32g .. 32g+31
+    static __device__ __forceinline__ int chunk(int ks, int g) { return 2 * g + ks; }
+    // fragments of half h: F[12 h + i] = w-tile i (i < 4), F[12 h + 4 + j] = x-tile j
+    template <bool FIRST>
+    static __device__ __forceinline__ void mfma(f32x4 (&acc)[4][8], frag (&F)[24]) {
+        static_for<0, 8>([&](auto jc) {
+            constexpr int j_ = decltype(jc)::value;
+            const f8x32 xb = __builtin_shufflevector(F[4 + j_], F[12 + 4 + j_], 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const f8x32 wa_ = __builtin_shufflevector(F[i], F[12 + i], 0, 1, 2, 3, 4, 5, 6, 7);
+                if constexpr (FIRST)
+                    acc[i][j_] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wa_, xb, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0, 0, 0, 0);
+                else
+                    acc[i][j_] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wa_, xb, acc[i][j_], 0, 0, 0, 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        });
+    }
+};
 
 struct F8Scales {
     const int* xe;      // [M] row exponents of x8
@@ -46,260 +48,25 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_nt8p_kernel(int M, int N, int
                                                                 const unsigned char* __restrict__ W, EpiB16 epi,
                                                                 OUT_T* __restrict__ out, int tiles_m, int tiles_n, int gm,
                                                                F8Scales sc) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int MT = 8, FS = 12, NF = 24;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int g = lane >> 4, c = lane & 15;
-    const int grp = wave >> 2, wq = wave & 3;       // group A / B; wave within the group
-    const int wm = wq >> 1, wn = 2 * grp + (wq & 1);
-    const int nk = K / 128;
-
-    // ---- this block's work items
-    const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3, cpx = gridDim.x >> 3;
-    const int P = (tiles_m - xcd + 7) >> 3;                 // m-panels of this XCD
-    const int n_x = P * tiles_n;
-    const int per = gm * tiles_n;
-    auto tile_of = [&](int l, int& tm, int& tn) {           // l-th tile of the XCD's walk
-        const int blk = l / per, r = l - blk * per;
-        const int gmb = min(gm, P - blk * gm);
-        tn = r / gmb;
-        tm = ((blk * gm + (r - tn * gmb)) << 3) + xcd;
-    };
-    const int nfull = jb < n_x ? (n_x - jb + cpx - 1) / cpx : 0;
-    const int nitems = nfull;
-    if (nitems == 0) return;
-    auto item_tile = [&](int idx) { return jb + cpx * idx; };
-    auto item_k0 = [&](int) { return 0; };
-    auto item_k1 = [&](int) { return nk; };
-
-    // ---- load side.  One piece = 1 KiB = 8 rows x 128 B; lane -> row l>>3, 16-byte slot l&7 holding chunk (l&7)^(row&7).
-    const int srow = lane >> 3, lchunk = (lane & 7) ^ srow;
-    // ONE per-lane byte offset per operand (piece 0 of this wave); pieces 1..3 are 8, 16, 24 rows further, which goes into the
-    // scalar offset of the load together with the k-step
-    const unsigned voffx = (unsigned)(((4 * wave) * 8 + srow) * K + lchunk * 16);     // x pieces 4*wave .. 4*wave+3 of 32
-    const unsigned voffw = (unsigned)(((4 * wq) * 8 + srow) * K + lchunk * 16);       // pieces 4*wq .. of the OTHER group's 16
-    const int piece_stride = 8 * K;                                                        // 8 rows, in bytes
-    const int og = grp ^ 1;
-    // two cursors through the same item sequence: x (k-step j+2) and the other group's w (A: j+1, B: j+2)
-    int ix = 0, kx = item_k0(0), kx1 = item_k1(0), iw = 0, kw = kx, kw1 = kx1;
-    __amdgpu_buffer_rsrc_t rx, rw;
-    auto set_x_tile = [&](int idx) {
-        int tm, tn;
-        tile_of(item_tile(idx), tm, tn);
-        const int m0 = tm * 256;
-        const int xr = min(256, M - m0);
-        rx = __builtin_amdgcn_make_buffer_rsrc((void*)(X + (long)m0 * K), 0, xr * K, 0x00020000);
-    };
-    auto set_w_tile = [&](int idx) {
-        int tm, tn;
-        tile_of(item_tile(idx), tm, tn);
-        const int n0 = tn * 256 + og * 128;
-        // (clamping both ways selects v_med3_i32, a VALU result: the descriptor then sits in VGPRs and every piece becomes a
-        // readfirstlane waterfall loop)
-        const int wr = __builtin_amdgcn_readfirstlane(max(0, min(128, N - n0)));
-        rw = __builtin_amdgcn_make_buffer_rsrc((void*)(W + (long)min(n0, N - 1) * K), 0, wr * K, 0x00020000);
-    };
-    int xls = 0, wls = 0;      // slots the cursors write next
-    auto issue_x = [&]() -> bool {      // this wave's 4 pieces of the x item at the cursor
-        if (ix >= nitems) return false;
-        char* dst = smem + xls * PP_X_BYTES + (4 * wave) * 1024;
+    pp_gemm_nt<PpFp8>(M, N, K, X, W, tiles_m, tiles_n, gm, [&](f32x4 (&acc)[4][8], int m0, int n0, int wm, int wn, int lane) {
+        // the row exponents: acc[n-tile i][m-tile j][q] belongs to row 16j + c, column 16i + 4g + q of the wave's 128 x 64
+        const int g = lane >> 4, c = lane & 15;
+        const int m_base = m0 + wm * 128 + c, n_base = n0 + wn * 64 + 4 * g;
+        float sr[8];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) f8_dma_piece(rx, dst + i * 1024, voffx, kx * 128 + i * piece_stride);
-        xls = (xls == 2) ? 0 : xls + 1;
-        if (++kx == kx1) {
-            if (++ix < nitems) {
-                kx = item_k0(ix);
-                kx1 = item_k1(ix);
-                set_x_tile(ix);
-            }
+        for (int j = 0; j < 8; ++j) sr[j] = __builtin_ldexpf(1.0f, sc.xe[min(m_base + 16 * j, M - 1)]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float sq[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) sq[q] = __builtin_ldexpf(1.0f, sc.we[min(n_base + 16 * i + q, N - 1)]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[i][j][q] *= sr[j] * sq[q];
         }
-        return true;
-    };
-    auto issue_w = [&]() -> bool {      // this wave's 4 pieces of the OTHER group's w sub-item at the cursor
-        if (iw >= nitems) return false;
-        char* dst = smem + PP_W_BASE + og * (2 * PP_W_BYTES) + wls * PP_W_BYTES + (4 * wq) * 1024;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) f8_dma_piece(rw, dst + i * 1024, voffw, kw * 128 + i * piece_stride);
-        wls ^= 1;
-        if (++kw == kw1) {
-            if (++iw < nitems) {
-                kw = item_k0(iw);
-                kw1 = item_k1(iw);
-                set_w_tile(iw);
-            }
-        }
-        return true;
-    };
-
-    set_x_tile(0);
-    set_w_tile(0);
-    // prologue = the issues of the "virtual" segments L_-2, L_-1:  A: X(0) | W_B(0), X(1);   B: W_A(0), X(0) | W_A(1), X(1)
-    if (grp == 0) {
-        issue_x();
-        issue_w();
-        issue_x();
-    } else {
-        issue_w();
-        issue_x();
-        issue_w();
-        issue_x();
-    }
-    // everything of k-step 0 (and, for B, of k-step 1: its first wait inside the loop comes too late for A's L_1) has landed
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (grp == 1) __builtin_amdgcn_s_barrier();     // B runs one segment behind
-
-    f32x4 acc[4][MT];
-    f8x16 F[NF];
-    const int sw = c & 7;
-    const unsigned lds0 = (unsigned)(size_t)smem;
-    const unsigned xoff = lds0 + (wm * 128 + c) * 128;
-    const unsigned woff = lds0 + PP_W_BASE + grp * (2 * PP_W_BYTES) + ((wq & 1) * 64 + c) * 128;
-    unsigned coff[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) coff[ks] = ((2 * g + ks) ^ sw) * 16;      // chunks 2g, 2g+1: k 32g .. 32g+31
-
-#ifdef F8_PROFILE_OFF
-    long p_t0 = clock64(), p_epi = 0, p_l = 0, p_lw = 0, p_c = 0, p_vm = 0, p_cb = 0, p_n = 1;
-#endif
-    int ic = 0, kc = item_k0(0), kc1 = item_k1(0), xrs = 0, wrs = 0;
-    // One k-step: L segment, barrier, C segment, the counted wait.  FIRST (the first k-step of an item) starts the accumulators
-    // from zero inside the MFMAs.  Two instantiations, called from a loop that is peeled by hand: with a run-time flag selecting
-    // the two MFMA forms inside ONE loop body the register allocator joins 128 accumulators from both and spills ~200 VGPRs.
-    auto kstep = [&](auto first_c) {
-        constexpr bool FIRST = decltype(first_c)::value;
-        // ------------------------------------------------ L segment
-#ifdef F8_PROFILE_OFF
-        long t0 = clock64();
-#endif
-        int issued = 0;
-        {
-            unsigned wa[2], xa[2];
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                wa[ks] = woff + wrs * PP_W_BYTES + coff[ks];
-                xa[ks] = xoff + xrs * PP_X_BYTES + coff[ks];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            static_for<0, PP_READS_FIRST>([&](auto fc) { f8_frag_read<decltype(fc)::value>(F[decltype(fc)::value], wa, xa); });
-            __builtin_amdgcn_sched_barrier(0);
-            if (issue_w()) issued += 4;
-            __builtin_amdgcn_sched_barrier(0);
-            static_for<PP_READS_FIRST, 24>([&](auto fc) { f8_frag_read<decltype(fc)::value>(F[decltype(fc)::value], wa, xa); });
-            __builtin_amdgcn_sched_barrier(0);
-            if (issue_x()) issued += 4;
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#ifdef F8_PROFILE_OFF
-        long t1 = clock64();
-#endif
-        // all 24 fragments in registers before the barrier: the slots may be refilled right after it
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(F[0]), "+v"(F[1]), "+v"(F[2]), "+v"(F[3]), "+v"(F[4]), "+v"(F[5]), "+v"(F[6]), "+v"(F[7]), "+v"(F[8]),
-                       "+v"(F[9]), "+v"(F[10]), "+v"(F[11]), "+v"(F[12]), "+v"(F[13]), "+v"(F[14]), "+v"(F[15]), "+v"(F[16]),
-                       "+v"(F[17]), "+v"(F[18]), "+v"(F[19]), "+v"(F[20]), "+v"(F[21]), "+v"(F[22]), "+v"(F[23]));
-        __builtin_amdgcn_s_barrier();
-#ifdef F8_PROFILE_OFF
-        long t2 = clock64();
-#endif
-        // ------------------------------------------------ C segment
-        __builtin_amdgcn_sched_barrier(0);
-        static_for<0, MT>([&](auto jc) {
-            constexpr int j_ = decltype(jc)::value;
-            const f8x32 xb = __builtin_shufflevector(F[4 + j_], F[FS + 4 + j_], 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const f8x32 wa_ = __builtin_shufflevector(F[i], F[FS + i], 0, 1, 2, 3, 4, 5, 6, 7);
-                if constexpr (FIRST)
-                    acc[i][j_] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wa_, xb, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0, 0, 0, 0);
-                else
-                    acc[i][j_] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wa_, xb, acc[i][j_], 0, 0, 0, 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        });
-#ifdef F8_PROFILE_OFF
-        long t3 = clock64();
-#endif
-        // what the readers after the coming barrier(s) need from this wave has landed: A leaves its x pieces (needed two barriers
-        // later, waited for at the end of its next C segment) in flight, B nothing.  (Before a tile's epilogue, so that no store
-        // is waited for.)
-        if (grp == 0 && issued == 8) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef F8_PROFILE_OFF
-        long t3b = clock64();
-        p_l += t1 - t0; p_lw += t2 - t1; p_c += t3 - t2; p_vm += t3b - t3; ++p_n;
-#endif
-        xrs = (xrs == 2) ? 0 : xrs + 1;
-        wrs ^= 1;
-    };
-    while (true) {
-        kstep(std::true_type{});
-        while (++kc != kc1) {
-#ifdef F8_PROFILE_OFF
-            long tb = clock64();
-#endif
-            __builtin_amdgcn_s_barrier();
-#ifdef F8_PROFILE_OFF
-            p_cb += clock64() - tb;
-#endif
-            kstep(std::false_type{});
-        }
-        // ---------------- end of an item.  Group A runs the epilogue AFTER the barrier that ends this interval, group B BEFORE it:
-        // both then sit in the same interval (A: epilogue + L_0 of the next tile; B: its last C segment + epilogue) instead of
-        // each group idling through the other's.  One call site, so one copy of the epilogue code.
-        if (grp == 0) __builtin_amdgcn_s_barrier();
-#ifdef F8_PROFILE_OFF
-        long te0 = clock64();
-#endif
-        int tm, tn;
-        tile_of(item_tile(ic), tm, tn);
-        {
-            // the row exponents: acc[n-tile i][m-tile j][q] belongs to row 16j + c, column 16i + 4g + q of the wave's 128 x 64
-            const int m_base = tm * 256 + wm * 128 + c, n_base = tn * 256 + wn * 64 + 4 * g;
-            float sr[MT];
-#pragma unroll
-            for (int j = 0; j < MT; ++j) sr[j] = __builtin_ldexpf(1.0f, sc.xe[min(m_base + 16 * j, M - 1)]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float sq[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) sq[q] = __builtin_ldexpf(1.0f, sc.we[min(n_base + 16 * i + q, N - 1)]);
-#pragma unroll
-                for (int j = 0; j < MT; ++j)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) acc[i][j][q] *= sr[j] * sq[q];
-            }
-        }
-        (void)nt_tile_epilogue<OUT_T, MT, FL, ACT>(acc, epi, out, M, N, tm * 256, tn * 256, wm, wn, lane);
-#ifdef F8_PROFILE_OFF
-        p_epi += clock64() - te0;
-#endif
-        if (grp == 1) __builtin_amdgcn_s_barrier();
-        if (++ic >= nitems) break;
-        kc = item_k0(ic);
-        kc1 = item_k1(ic);
-    }
-    if (grp == 0) __builtin_amdgcn_s_barrier();     // the barrier that ends B's last C segment
-}
-
-template <int FL, int ACT>
-static int launch_f8(int M, int N, int K, const unsigned char* X, const unsigned char* W, const F8Scales& sc, const EpiB16& epi,
-                     bf16_t* out, int n_cu, hipStream_t stream) {
-    const int tiles_m = cdiv(M, 256), tiles_n = cdiv(N, 256);
-    const int gm = nt_pick_gm(N, K, tiles_m);
-    const int per_xcd = ((tiles_m + 7) >> 3) * tiles_n;
-    const int grid = per_xcd * 8 < n_cu ? per_xcd * 8 : n_cu;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)gemm_fp8_nt8p_kernel<bf16_t, FL, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)PP_LDS);
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((gemm_fp8_nt8p_kernel<bf16_t, FL, ACT>), dim3(grid), dim3(512), PP_LDS, stream, M, N, K, X, W, epi, out,
-                       tiles_m, tiles_n, gm, sc);
-    CLIPX_LAUNCH_CHECK();
-    return 0;
+        (void)nt_tile_epilogue<OUT_T, 8, FL, ACT>(acc, epi, out, M, N, m0, n0, wm, wn, lane);
+    });
 }
 
 // y = epi(x8 . w8^T) for e4m3 operands with per-row exponents; bf16 output.  Needs K % 128 == 0.
@@ -310,40 +77,15 @@ int launch_gemm_fp8_nt(int M, int N, int K, const unsigned char* X, const int* x
                 "fp8 NT GEMM: operands must be 16-B aligned");
     CLIPX_CHECK((long)256 * K < (1l << 31), "fp8 NT GEMM: K too large");
     if (M <= 0 || N <= 0) return 0;
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-        if (n_cu <= 0) n_cu = 256;
-        n_cu = (n_cu / 8) * 8;
-        if (n_cu < 8) n_cu = 8;
-    }
-    F8Scales sc{xe, we};
-    int fl = 0;
-    if (epi.bias) fl |= F_BIAS;
-    if (epi.residual) fl |= F_RES;
-    if (epi.act_u) fl |= F_ACTU;
-    if (epi.act != CLIPX_ACT_NONE) fl |= F_ACT;
-    if (epi.preact) fl |= F_PRE;
-    if (epi.pre8) fl |= F_PRE8;
-    if (epi.actu8) fl |= F_ACTU8;
-    CLIPX_CHECK(!((fl & F_ACTU) && (fl & F_ACT)), "fp8 NT GEMM: act and act_u are mutually exclusive");
+    const int n_cu = clipx_num_cu(false);
+    const F8Scales sc{xe, we};
+    int fl, act;
+    CLIPX_CHECK(nt_epi_flags(epi, fl, act), "fp8 NT GEMM: act and act_u are mutually exclusive");
     CLIPX_CHECK(!epi.ms_max, "fp8 NT GEMM: the MaxSim epilogue is built for the bf16 kernel only");
-    const int act = (fl & F_ACTU) ? epi.act_u_kind : ((fl & F_ACT) ? epi.act : CLIPX_ACT_NONE);
-#define F8_CASE(FLV, ACTV) \
-    if (fl == (FLV) && act == (ACTV)) return launch_f8<(FLV), (ACTV)>(M, N, K, X, W, sc, epi, out, n_cu, stream)
-    F8_CASE(0, CLIPX_ACT_NONE);
-    F8_CASE(F_BIAS, CLIPX_ACT_NONE);
-    F8_CASE(F_BIAS | F_RES, CLIPX_ACT_NONE);
-    F8_CASE(F_ACTU, CLIPX_ACT_GELU);
-    F8_CASE(F_ACTU, CLIPX_ACT_QUICKGELU);
-    F8_CASE(F_BIAS | F_ACT | F_PRE, CLIPX_ACT_GELU);
-    F8_CASE(F_BIAS | F_ACT | F_PRE, CLIPX_ACT_QUICKGELU);
-    F8_CASE(F_BIAS | F_ACT, CLIPX_ACT_GELU);
-    F8_CASE(F_BIAS | F_ACT, CLIPX_ACT_QUICKGELU);
-    F8_CASE(F_BIAS | F_ACT | F_PRE8, CLIPX_ACT_GELU);         // c_fc (training): GELU' kept on eight bits (gemm_epi.h)
-    F8_CASE(F_ACTU8, CLIPX_ACT_NONE);                         // c_proj dgrad x the kept factor
+#define F8_CASE(FLV, ACTV)             \
+    if (fl == (FLV) && act == (ACTV)) \
+    return pp_launch<gemm_fp8_nt8p_kernel<bf16_t, (FLV), (ACTV)>>(M, N, K, X, W, epi, out, n_cu, stream, sc)
+    NT_EPI_CASES(F8_CASE)
 #undef F8_CASE
     clipx_set_error("fp8 NT GEMM: epilogue combination not built (flags %d, act %d)", fl, act);
     return -1;

@@ -15,6 +15,35 @@
 #define NT_FULL_LINE 0   // 1: epilogue stores cover whole 128-byte lines per instruction (measured: same FETCH_SIZE, same time)
 #endif
 
+// The epilogue an EpiB16 asks for, as the kernels' template arguments: fl = operand flags, act = the one activation kind in play
+// (act_u's or act's).  false: act and act_u are both set, which no kernel builds.
+static inline bool nt_epi_flags(const EpiB16& epi, int& fl, int& act) {
+    fl = 0;
+    if (epi.bias) fl |= F_BIAS;
+    if (epi.residual) fl |= F_RES;
+    if (epi.act_u) fl |= F_ACTU;
+    if (epi.act != CLIPX_ACT_NONE) fl |= F_ACT;
+    if (epi.preact) fl |= F_PRE;
+    if (epi.pre8) fl |= F_PRE8;
+    if (epi.actu8) fl |= F_ACTU8;
+    act = (fl & F_ACTU) ? epi.act_u_kind : ((fl & F_ACT) ? epi.act : CLIPX_ACT_NONE);
+    return !((fl & F_ACTU) && (fl & F_ACT));
+}
+// the (flags, activation) pairs that the one-barrier, the ping-pong and the fp8 kernel all build; CASE(flags, act) is the
+// dispatcher's own "if it is this one, launch it"
+#define NT_EPI_CASES(CASE)                                                                                       \
+    CASE(0, CLIPX_ACT_NONE);                             /* dgrad, patch embedding, projections */               \
+    CASE(F_BIAS, CLIPX_ACT_NONE);                        /* in_proj */                                           \
+    CASE(F_BIAS | F_RES, CLIPX_ACT_NONE);                /* out_proj, c_proj (+ residual stream) */              \
+    CASE(F_ACTU, CLIPX_ACT_GELU);                        /* c_proj dgrad x GELU'(u) */                           \
+    CASE(F_ACTU, CLIPX_ACT_QUICKGELU);                                                                           \
+    CASE(F_BIAS | F_ACT | F_PRE, CLIPX_ACT_GELU);        /* c_fc (training: keeps the pre-activation) */         \
+    CASE(F_BIAS | F_ACT | F_PRE, CLIPX_ACT_QUICKGELU);                                                           \
+    CASE(F_BIAS | F_ACT, CLIPX_ACT_GELU);                /* c_fc (no_grad) */                                    \
+    CASE(F_BIAS | F_ACT, CLIPX_ACT_QUICKGELU);                                                                   \
+    CASE(F_BIAS | F_ACT | F_PRE8, CLIPX_ACT_GELU);       /* c_fc (training): GELU' kept on eight bits (gemm_epi.h) */ \
+    CASE(F_ACTU8, CLIPX_ACT_NONE);                       /* c_proj dgrad x the kept factor */
+
 template <typename OUT_T, int MT, int FL>
 constexpr int nt_epilogue_stores() {
     return std::is_same<OUT_T, bf16_t>::value ? ((FL & F_PRE) ? 4 * MT : 2 * MT) + ((FL & F_PRE8) ? MT : 0) : 0;

@@ -51,6 +51,11 @@ int launch_gemm_bf16_tn_group(int M, int nprob, const int* N, const int* K, cons
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
     __builtin_amdgcn_global_load_lds((const GLOBAL_PTR(void))gsrc, (LDS_PTR(void))lds_dst, 16, 0, 0);
 }
+// one LDS-DMA piece through a buffer descriptor (a plain __device__ function: inside a kernel's nested generic lambdas the
+// builtin silently suppressed the HOST-side instantiation of the whole kernel template -- undefined stubs at load time)
+__device__ __forceinline__ void lds_dma_piece(__amdgpu_buffer_rsrc_t rsrc, char* lds_dst, unsigned voff, int soff) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LDS_PTR(void))lds_dst, 16, voff, soff, 0, 0);
+}
 
 __device__ __forceinline__ bf16x8 lds_read8(const char* p) { return *reinterpret_cast<const bf16x8*>(p); }
 

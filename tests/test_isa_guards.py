@@ -57,13 +57,22 @@ def _read_burst_heads(body, read_mnemonic, window=8):
     return heads
 
 
+# bytes/lane of scratch that an instantiation had when its kernel came under the guard below (see its docstring); an upper bound
+_KNOWN_SCRATCH = {"_Z20gemm_fp8_nt8p_kernelIDF16bLi25ELi1E": 8, "_Z20gemm_fp8_nt8p_kernelIDF16bLi73ELi1E": 24}
+
+
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 @pytest.mark.parametrize("src,prefix,read", [("gemm_bf16_nt.hip", "_Z19gemm_bf16_nt_kernel", "ds_read_b128"),
                                              ("gemm_bf16_tn.hip", "_Z19gemm_bf16_tn_kernel", "ds_read_b64_tr_b16"),
                                              ("gemm_bf16_nt8p.hip", "_Z21gemm_bf16_nt8p_kernel", "ds_read_b128"),
+                                             ("gemm_fp8_nt8p.hip", "_Z20gemm_fp8_nt8p_kernel", "ds_read_b128"),
                                              ("gemm_bf16_tn.hip", "_Z22gemm_bf16_tn_pp_kernel", "ds_read_b64_tr_b16"),
                                              ("gemm_bf16_tn.hip", "_Z23gemm_bf16_tn_ppg_kernel", "ds_read_b64_tr_b16")])
 def test_no_ring_drain_and_no_spills(src, prefix, read, tmp_path):
+    """No compiler-inserted vmcnt(0) in front of the fragment reads, and no scratch.  A recorded finding, not a licence: two fp8
+    ping-pong instantiations already spilled when this guard was extended to that kernel -- <bf16, 25, 1> (bias + GELU +
+    pre-activation) 8 bytes/lane and <bf16, 73, 1> (bias + GELU + eight-bit GELU', the training c_fc under fp8_mfma) 24 bytes/lane.
+    _KNOWN_SCRATCH pins them at those figures until they are fixed; every other instantiation stays at 0."""
     asm, remarks = _asm(src, tmp_path)
     kernels = _kernels(asm, prefix)
     assert kernels, "no kernels found"
@@ -75,7 +84,8 @@ def test_no_ring_drain_and_no_spills(src, prefix, read, tmp_path):
     for m in re.finditer(r"Function Name: (\S+).*?ScratchSize \[bytes/lane\]: (\d+)", remarks, re.S):
         name, scratch = m.group(1), int(m.group(2))
         if name.startswith(prefix) and "Li27E" not in name:
-            assert scratch == 0, f"{name} spills {scratch} bytes/lane"
+            allowed = next((b for k, b in _KNOWN_SCRATCH.items() if name.startswith(k)), 0)
+            assert scratch <= allowed, f"{name} spills {scratch} bytes/lane (allowed: {allowed})"
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
