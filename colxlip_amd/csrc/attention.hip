@@ -3,8 +3,8 @@
 // whole sequence resident in LDS, so scores never touch HBM and the kernels are HBM-bound on
 // qkv / dout / dqkv traffic.
 //
-// bf16 kernels (head dim 64, L <= 224): all products on v_mfma_f32_16x16x32_bf16, arranged so that no
-// computed tile ever moves between lanes:
+// bf16 kernels (head dim 64, L <= 128; longer sequences and head dim 80 on the online-softmax kernels further down): all products
+// on v_mfma_f32_16x16x32_bf16, arranged so that no computed tile ever moves between lanes:
 //   S^T = K.Q^T       (key rows in registers, query on the lane)  -> softmax is lane-local + 2 shuffles
 //   O^T = V^T.P^T     A operand = V read through ds_read_b64_tr_b16, B operand = the S^T accumulator itself
 // and in backward the same trick in both orientations (dQ from S^T/dP^T tiles, dK/dV from S/dP tiles).
@@ -169,61 +169,30 @@ __global__ __launch_bounds__(128) void attn_f32_bwd_kernel(int L, int heads, int
 }
 
 // =============================================================================== bf16 MFMA kernels
-#define AT_HD 64
-// minimum waves per SIMD asked of the compiler (caps VGPRs): whole blocks must fit, 16 / 20 / 24 waves per CU
+// minimum waves per SIMD asked of the compiler (caps VGPRs): whole blocks must fit
 #ifndef AT_MINW_S
 #define AT_MINW_S 4      // NT <= 4 (blocks of <= 4 waves)
 #endif
 #ifndef AT_MINW_M
 #define AT_MINW_M 3      // NT 5..8 (170 VGPRs: no spills in the backward; L=77 backward 686 -> 650 us vs 4 / 128 VGPRs)
 #endif
-#define AT_MINW(NT) ((NT) <= 4 ? AT_MINW_S : ((NT) <= 8 ? AT_MINW_M : 2))
-#define AT_ROWB 128   // bytes per LDS row (64 bf16)
+#define AT_MINW(NT) ((NT) <= 4 ? AT_MINW_S : AT_MINW_M)
 
-__device__ __forceinline__ int at_off(int row, int chunk) {
-    return row * AT_ROWB + ((chunk ^ (((row >> 1) & 3) << 1)) << 4);
-}
+// ---- LDS image of an operand and its MFMA fragments, for every bf16 kernel below.  Per head dim:
+//   HD = 64: 128-byte rows;
+//   HD = 80: rows padded to 128 elements = 256 bytes (dims 80..127 zero), three 32-deep k-slices, five 16-column output tiles.
+template <int HD> struct AtCfg {
+    static constexpr int ROWB = HD <= 64 ? 128 : 256;      // LDS row bytes
+    static constexpr int KS = (HD + 31) / 32;              // 32-deep k-slices of the QK^T reduction
+    static constexpr int DT = (HD + 15) / 16;              // 16-column tiles of the head dim
+    static constexpr int CHUNKS = HD / 8;                  // valid 16-byte chunks per row
+    static constexpr int MAXW_F = HD <= 64 ? 16 : 12;      // online-softmax kernels: waves per block, forward (head dim 80 with the fast path: > 128 VGPRs)
+    static constexpr int MAXW_B = HD <= 64 ? 16 : 12;      // backward: head dim 80 needs 168 VGPRs -> three waves per SIMD
+    static constexpr int STAGE_U = HD <= 64 ? 5 : 6;       // online-softmax kernels: unroll of at_stage2 (see there)
+};
+constexpr int AT_HD = 64;                                   // the whole-sequence kernels' head dim and LDS row bytes
+constexpr int AT_ROWB = AtCfg<AT_HD>::ROWB;
 
-// stage rows [0, LP) of one operand (row stride `ld` elements in HBM) into its LDS image; rows >= L -> 0
-// Both operands of a phase at once, loads first: the plain loop (load, wait, write LDS, next chunk) was a chain of HBM
-// latencies per thread -- 4 chunks x 2 operands with 3-wave blocks; here up to 8 loads per thread are in flight.
-__device__ __forceinline__ void at_stage2(char* ldsA, const bf16_t* srcA, long ldA, char* ldsB, const bf16_t* srcB, long ldB,
-                                          int L, int LP) {
-    constexpr int U = 4;
-    const int total = LP * 8, step = blockDim.x;
-    for (int base = threadIdx.x; base < total; base += U * step) {
-        uint4 va[U], vb[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int id = base + u * step, row = id >> 3, ch = id & 7;
-            va[u] = make_uint4(0u, 0u, 0u, 0u);
-            vb[u] = make_uint4(0u, 0u, 0u, 0u);
-            if (id < total && row < L) {
-                va[u] = *reinterpret_cast<const uint4*>(srcA + (long)row * ldA + ch * 8);
-                vb[u] = *reinterpret_cast<const uint4*>(srcB + (long)row * ldB + ch * 8);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int id = base + u * step, row = id >> 3, ch = id & 7;
-            if (id < total) {
-                *reinterpret_cast<uint4*>(ldsA + at_off(row, ch)) = va[u];
-                *reinterpret_cast<uint4*>(ldsB + at_off(row, ch)) = vb[u];
-            }
-        }
-    }
-}
-
-// row-read fragment: rows 16*tile + c, reduction chunk 4*ks + g
-__device__ __forceinline__ bf16x8 at_row_frag(const char* img, int tile, int ks, int g, int c) {
-    return lds_read8(img + at_off(16 * tile + c, 4 * ks + g));
-}
-// transposed fragment: reduction rows 32*s + {4g+q, 16+4g+q}, columns of 16-wide tile dt
-__device__ __forceinline__ bf16x8 at_tr_frag(const char* img, int s, int dt, int g, int q, int p) {
-    const int r0 = 32 * s + 4 * g + q, r1 = r0 + 16;
-    const int ch = 2 * dt + (p >> 1), hb = (p & 1) * 8;
-    return lds_tr8(img + at_off(r0, ch) + hb, img + at_off(r1, ch) + hb);
-}
 __device__ __forceinline__ bf16x8 pack_pair(const f32x4& a, const f32x4& b) {
     bf16x8 r;
     r[0] = (bf16_t)a[0]; r[1] = (bf16_t)a[1]; r[2] = (bf16_t)a[2]; r[3] = (bf16_t)a[3];
@@ -238,24 +207,79 @@ __device__ __forceinline__ float group_sum(float v) {
     v += __shfl_xor(v, 16, 64);
     return v + __shfl_xor(v, 32, 64);
 }
-
+// Swizzle of the 16-byte chunks of a row.  A 16-lane group of ds_read_b128 (rows c, chunk 4ks+g) and a 32-lane group of
+// ds_read_b64_tr_b16 (eight consecutive rows, 32 bytes each) must land on 256 distinct bytes of the 64 banks:
+//   128-byte rows: odd rows already sit in the other half of the banks; xor with 2 * ((row >> 1) & 3) inside the 8 chunks
+//   256-byte rows: every row starts on bank 0, so the xor needs three row bits: 2 * (row & 7) inside the 16 chunks
+//                  (with the 128-byte rule rows 2i and 2i+1 collided: every fragment read of the head-dim-80 kernels 2-way)
+template <int ROWB>
+__device__ __forceinline__ int at_off(int row, int chunk) {
+    if constexpr (ROWB == 256) return row * ROWB + ((chunk ^ ((row & 7) << 1)) << 4);
+    return row * ROWB + ((chunk ^ (((row >> 1) & 3) << 1)) << 4);
+}
+// stage rows [0, LP) of two operands (row stride `ld` elements in HBM) into their LDS images; rows >= L -> 0.
+// Both operands of a phase at once, loads first: the plain loop (load, wait, write LDS, next chunk) was a chain of HBM
+// latencies per thread -- 4 chunks x 2 operands with 3-wave blocks; here U x 2 loads per thread are in flight.
+// U = 4 in the whole-sequence kernels.  The online-softmax kernels take 5 (head dim 64) or 6 (80): with a full block (16 x 64
+// threads at head dim 64, 12 x 64 at 80) ONE batch covers both operand images, i.e. one HBM round trip per staging instead of two
+// or three (nothing else runs on the CU meanwhile: the images of one (sample, head) fill its LDS)
+template <int HD, int U>
+__device__ __forceinline__ void at_stage2(char* ldsA, const bf16_t* srcA, long ldA, char* ldsB, const bf16_t* srcB, long ldB,
+                                          int L, int LP) {
+    constexpr int RC = AtCfg<HD>::ROWB / 16;
+    const int total = LP * RC, step = blockDim.x;
+    for (int base = threadIdx.x; base < total; base += U * step) {
+        uint4 va[U], vb[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int id = base + u * step, row = id / RC, ch = id % RC;
+            va[u] = make_uint4(0u, 0u, 0u, 0u);
+            vb[u] = make_uint4(0u, 0u, 0u, 0u);
+            if (id < total && row < L && ch < AtCfg<HD>::CHUNKS) {
+                va[u] = *reinterpret_cast<const uint4*>(srcA + (long)row * ldA + ch * 8);
+                vb[u] = *reinterpret_cast<const uint4*>(srcB + (long)row * ldB + ch * 8);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int id = base + u * step, row = id / RC, ch = id % RC;
+            if (id < total) {
+                *reinterpret_cast<uint4*>(ldsA + at_off<AtCfg<HD>::ROWB>(row, ch)) = va[u];
+                *reinterpret_cast<uint4*>(ldsB + at_off<AtCfg<HD>::ROWB>(row, ch)) = vb[u];
+            }
+        }
+    }
+}
+// row-read fragment: rows 16*tile + c, reduction chunk 4*ks + g
+template <int HD>
+__device__ __forceinline__ bf16x8 at_row_frag(const char* img, int tile, int ks, int g, int c) {
+    return lds_read8(img + at_off<AtCfg<HD>::ROWB>(16 * tile + c, 4 * ks + g));
+}
+// transposed fragment: reduction rows 32*s + {4g+q, 16+4g+q}, columns of 16-wide tile dt
+template <int HD>
+__device__ __forceinline__ bf16x8 at_tr_frag(const char* img, int s, int dt, int g, int q, int p) {
+    const int r0 = 32 * s + 4 * g + q, r1 = r0 + 16;
+    const int ch = 2 * dt + (p >> 1), hb = (p & 1) * 8;
+    return lds_tr8(img + at_off<AtCfg<HD>::ROWB>(r0, ch) + hb, img + at_off<AtCfg<HD>::ROWB>(r1, ch) + hb);
+}
 // fragment straight from HBM/L2 (an operand tile that only this wave reads): rows 16*tile + c, chunk 4*ks + g
+template <int HD>
 __device__ __forceinline__ bf16x8 at_global_frag(const bf16_t* src, long ld, int L, int tile, int ks, int g, int c) {
-    const int row = 16 * tile + c;
+    const int row = 16 * tile + c, ch = 4 * ks + g;
     uint4 v = make_uint4(0u, 0u, 0u, 0u);
-    if (row < L) v = *reinterpret_cast<const uint4*>(src + (long)row * ld + (4 * ks + g) * 8);
+    if (row < L && ch < AtCfg<HD>::CHUNKS) v = *reinterpret_cast<const uint4*>(src + (long)row * ld + ch * 8);
     union { uint4 u; bf16x8 f; } x;
     x.u = v;
     return x.f;
 }
-
 
 // Store one 16-row x 64-column fp32 accumulator tile (lane (g,c): row c, columns 16*dt + 4*g + 0..3 in o[dt]) as bf16,
 // coalesced: in the accumulator layout neighbouring lanes are neighbouring ROWS and each holds 8 bytes per 16-column
 // tile, i.e. four 8-byte stores whose lanes all hit different cache lines (measured for the GEMM epilogue,
 // scripts/ubench_store.hip: 13.7 B/clk per CU for such 16-byte stores, 50 B/clk when four neighbouring lanes cover 64
 // contiguous bytes).  v_permlane16_swap pairs two 16-column tiles into 16-byte chunks, ds_bpermute (crossbar only) moves
-// lane 16*g + c to lane 4*c + chunk: two 16-byte stores, each 16 rows x 64 contiguous bytes.
+// lane 16*g + c to lane 4*c + chunk: two 16-byte stores, each 16 rows x 64 contiguous bytes.  A fifth 16-column tile (HD = 80)
+// goes out with 8-byte stores.
 typedef unsigned at_u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned at_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ unsigned at_pack2(float a, float b) {
@@ -264,7 +288,9 @@ __device__ __forceinline__ unsigned at_pack2(float a, float b) {
     x.h[1] = (bf16_t)b;
     return x.u;
 }
-__device__ __forceinline__ void at_store_tile(bf16_t* dst, long ld, int L, int row0, const f32x4 (&o)[4], float mul, int lane) {
+template <int HD>
+__device__ __forceinline__ void at_store_tile(bf16_t* dst, long ld, int L, int row0, const f32x4 (&o)[AtCfg<HD>::DT], float mul,
+                                              int lane) {
     const int srow = lane >> 2, sch = lane & 3;
     const int bp_src = 4 * (16 * (((sch & 1) << 1) | (sch >> 1)) + srow);
     unsigned lo[4], hi[4];
@@ -283,13 +309,18 @@ __device__ __forceinline__ void at_store_tile(bf16_t* dst, long ld, int L, int r
         for (int d = 0; d < 4; ++d) t[d] = (unsigned)__builtin_amdgcn_ds_bpermute(bp_src, (int)q[d]);
         if (row0 + srow < L) *reinterpret_cast<at_u32x4*>(dst + (long)(row0 + srow) * ld + 8 * sch + 32 * ip) = t;
     }
+    if constexpr (AtCfg<HD>::DT > 4) {
+        const int g = lane >> 4, c = lane & 15;
+        if (row0 + c < L)
+            store4(dst + (long)(row0 + c) * ld + 64 + 4 * g, make_float4(o[4][0] * mul, o[4][1] * mul, o[4][2] * mul, o[4][3] * mul));
+    }
 }
 
-
+// ---- whole-sequence kernels: head dim 64, L <= 128 (NT = 2, 4, 6 or 8 tiles of 16 rows)
 // CAUSAL / PACKED as in attn_bf16_bwd4_kernel below (round 4): key masks only in the tile that holds rows behind L and in the
 // diagonal tile of a causal sequence, tiles above the diagonal skipped whole, the scale inside the exponent's packed FMA.
 template <int NT, bool CAUSAL, bool PACKED>
-__global__ __launch_bounds__((NT <= 8 ? 64 * NT : 32 * (NT + 1)), AT_MINW(NT)) void attn_bf16_fwd_kernel(int L, int heads,
+__global__ __launch_bounds__(64 * NT, AT_MINW(NT)) void attn_bf16_fwd_kernel(int L, int heads,
                                                             const bf16_t* __restrict__ qkv,
                                                             bf16_t* __restrict__ out,
     const int* __restrict__ seq_ids, const int* __restrict__ cu_rows) {
@@ -312,10 +343,10 @@ __global__ __launch_bounds__((NT <= 8 ? 64 * NT : 32 * (NT + 1)), AT_MINW(NT)) v
     bf16x8 qpre0, qpre1;
     {
         const int lane0 = threadIdx.x & 63, w0 = threadIdx.x >> 6;
-        qpre0 = at_global_frag(base, 3 * d, L, w0, 0, lane0 >> 4, lane0 & 15);
-        qpre1 = at_global_frag(base, 3 * d, L, w0, 1, lane0 >> 4, lane0 & 15);
+        qpre0 = at_global_frag<AT_HD>(base, 3 * d, L, w0, 0, lane0 >> 4, lane0 & 15);
+        qpre1 = at_global_frag<AT_HD>(base, 3 * d, L, w0, 1, lane0 >> 4, lane0 & 15);
     }
-    at_stage2(Ks, base + d, 3 * d, Vs, base + 2 * d, 3 * d, L, LP);
+    at_stage2<AT_HD, 4>(Ks, base + d, 3 * d, Vs, base + 2 * d, 3 * d, L, LP);
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
@@ -325,18 +356,18 @@ __global__ __launch_bounds__((NT <= 8 ? 64 * NT : 32 * (NT + 1)), AT_MINW(NT)) v
     const f32x2 sc22 = {sc2, sc2};
     const int ntq = PACKED ? (L + 15) >> 4 : NT;
     const bool ragged = (L & 15) != 0;
-    const int kq0 = at_off(c, g), kq1 = at_off(c, 4 + g);
+    const int kq0 = at_off<AT_ROWB>(c, g), kq1 = at_off<AT_ROWB>(c, 4 + g);
     int vt[4];
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) vt[dt] = at_off(4 * g + q, 2 * dt + (p >> 1)) + (p & 1) * 8;
+    for (int dt = 0; dt < 4; ++dt) vt[dt] = at_off<AT_ROWB>(4 * g + q, 2 * dt + (p >> 1)) + (p & 1) * 8;
 
     const int nwaves = blockDim.x >> 6;
     for (int qt = wave; qt < ntq; qt += nwaves) {
         const int query = 16 * qt + c;
         bf16x8 qf0 = qpre0, qf1 = qpre1;
         if (qt != wave) {      // only when a block has fewer waves than query tiles
-            qf0 = at_global_frag(base, 3 * d, L, qt, 0, g, c);
-            qf1 = at_global_frag(base, 3 * d, L, qt, 1, g, c);
+            qf0 = at_global_frag<AT_HD>(base, 3 * d, L, qt, 0, g, c);
+            qf1 = at_global_frag<AT_HD>(base, 3 * d, L, qt, 1, g, c);
         }
         f32x4 s[NT];
         float m = -INFINITY;
@@ -386,173 +417,19 @@ __global__ __launch_bounds__((NT <= 8 ? 64 * NT : 32 * (NT + 1)), AT_MINW(NT)) v
                         lds_tr8(Vs + sp * 4096 + vt[dt], Vs + sp * 4096 + 2048 + vt[dt]), pf, o[dt], 0, 0, 0);
             }
         }
-        at_store_tile(out + row0 * d + h * AT_HD, d, L, 16 * qt, o, inv_l, lane);
+        at_store_tile<AT_HD>(out + row0 * d + h * AT_HD, d, L, 16 * qt, o, inv_l, lane);
     }
 }
 
-// Backward.  Two phases that reuse the same two LDS images (so a (sample, head) needs 2*LP*128 B, not 4*LP*128 B,
-// and each phase's registers are dead in the other):
-//   A  K,V in LDS; wave = one 16-query tile (Q, dO fragments straight from memory): S^T, dP^T -> lse, delta, dQ
-//   B  Q,dO in LDS; wave = one 16-key tile (K, V fragments from memory, L2-warm): S, dP -> dV, dK
-template <int NT>
-__global__ __launch_bounds__((NT <= 8 ? 64 * NT : 32 * (NT + 1)), AT_MINW(NT)) void attn_bf16_bwd_kernel(
-    int L, int heads, int causal, const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
-    bf16_t* __restrict__ dqkv,
-    const int* __restrict__ seq_ids, const int* __restrict__ cu_rows) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int LP = 16 * NT;
-    char* R0 = smem;                          // phase A: K      phase B: Q
-    char* R1 = smem + LP * AT_ROWB;           // phase A: V      phase B: dO
-    float* lse2 = reinterpret_cast<float*>(smem + 2 * LP * AT_ROWB);
-    float* delta = lse2 + LP;
-    const int b = blockIdx.x / heads, h = blockIdx.x % heads;
-    long row0 = (long)b * L;
-    if (cu_rows) {           // packed rows: this block's sequence starts at cu_rows[s] and has cu_rows[s+1]-cu_rows[s] rows
-        const int s_ = seq_ids ? seq_ids[b] : b;
-        row0 = cu_rows[s_];
-        L = cu_rows[s_ + 1] - cu_rows[s_];
-    }
-    const int d = heads * AT_HD;
-    const long ld3 = 3 * d;
-    const bf16_t* qbase = qkv + row0 * ld3 + h * AT_HD;
-    const bf16_t* gbase = dout + row0 * d + h * AT_HD;
-    bf16_t* dbase = dqkv + row0 * ld3 + h * AT_HD;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int nwaves = blockDim.x >> 6;
-    const int g = lane >> 4, c = lane & 15, q = c >> 2, p = c & 3;
-    const float scale = rsqrtf((float)AT_HD);
-    const float sc2 = scale * 1.44269504088896340736f;
-    const int nt_used = (L + 15) >> 4;
-    at_stage2(R0, qbase + d, ld3, R1, qbase + 2 * d, ld3, L, LP);
-    for (int i = threadIdx.x; i < LP; i += blockDim.x) { lse2[i] = 1e30f; delta[i] = 0.f; }
-    __syncthreads();
-
-    // ---- phase A
-    for (int qt = wave; qt < nt_used; qt += nwaves) {
-        const int query = 16 * qt + c;
-        const bf16x8 qf0 = at_global_frag(qbase, ld3, L, qt, 0, g, c), qf1 = at_global_frag(qbase, ld3, L, qt, 1, g, c);
-        const bf16x8 gf0 = at_global_frag(gbase, d, L, qt, 0, g, c), gf1 = at_global_frag(gbase, d, L, qt, 1, g, c);
-        f32x4 s[NT], dp[NT];
-        float m2 = -INFINITY;
-#pragma unroll
-        for (int kt = 0; kt < NT; ++kt) {
-            f32x4 a = {0.f, 0.f, 0.f, 0.f}, e = {0.f, 0.f, 0.f, 0.f};
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_row_frag(R0, kt, 0, g, c), qf0, a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_row_frag(R0, kt, 1, g, c), qf1, a, 0, 0, 0);
-            e = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_row_frag(R1, kt, 0, g, c), gf0, e, 0, 0, 0);
-            e = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_row_frag(R1, kt, 1, g, c), gf1, e, 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int key = 16 * kt + 4 * g + r;
-                const bool ok = key < L && !(causal && key > query);
-                a[r] = ok ? a[r] * sc2 : -INFINITY;
-                m2 = fmaxf(m2, a[r]);
-            }
-            s[kt] = a;
-            dp[kt] = e;
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        m2 = group_max(m2);
-        float l = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float e = __builtin_amdgcn_exp2f(s[kt][r] - m2);
-                s[kt][r] = e;
-                l += e;
-            }
-        l = group_sum(l);
-        const float inv_l = 1.0f / l;
-        float dl = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                s[kt][r] *= inv_l;
-                dl += s[kt][r] * dp[kt][r];
-            }
-        dl = group_sum(dl);
-        if (g == 0) {
-            lse2[query] = m2 + log2f(l);
-            delta[query] = dl;
-        }
-#pragma unroll
-        for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) s[kt][r] = s[kt][r] * (dp[kt][r] - dl) * scale;   // dS^T
-        f32x4 dq[4];
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) dq[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int sp = 0; sp < NT / 2; ++sp) {
-            const bf16x8 df = pack_pair(s[2 * sp], s[2 * sp + 1]);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-                dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_tr_frag(R0, sp, dt, g, q, p), df, dq[dt], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        at_store_tile(dbase, ld3, L, 16 * qt, dq, 1.0f, lane);
-    }
-    __syncthreads();                           // everyone is done with K, V; lse/delta are complete
-    at_stage2(R0, qbase, ld3, R1, gbase, d, L, LP);     // Q (L2-warm: this block just read these rows), dO
-    __syncthreads();
-
-    // ---- phase B
-    for (int kt = wave; kt < nt_used; kt += nwaves) {
-        const int key = 16 * kt + c;
-        const bf16x8 kf0 = at_global_frag(qbase + d, ld3, L, kt, 0, g, c), kf1 = at_global_frag(qbase + d, ld3, L, kt, 1, g, c);
-        const bf16x8 vf0 = at_global_frag(qbase + 2 * d, ld3, L, kt, 0, g, c), vf1 = at_global_frag(qbase + 2 * d, ld3, L, kt, 1, g, c);
-        f32x4 dv[4], dk[4];
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) { dv[dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; dk[dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-        for (int sp = 0; sp < NT / 2; ++sp) {
-            f32x4 pt[2], dst[2];
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                const int qt = 2 * sp + hh;
-                f32x4 a = {0.f, 0.f, 0.f, 0.f}, e = {0.f, 0.f, 0.f, 0.f};
-                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_row_frag(R0, qt, 0, g, c), kf0, a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_row_frag(R0, qt, 1, g, c), kf1, a, 0, 0, 0);
-                e = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_row_frag(R1, qt, 0, g, c), vf0, e, 0, 0, 0);
-                e = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_row_frag(R1, qt, 1, g, c), vf1, e, 0, 0, 0);
-                const f32x4 ls = *reinterpret_cast<const f32x4*>(lse2 + 16 * qt + 4 * g);
-                const f32x4 dl = *reinterpret_cast<const f32x4*>(delta + 16 * qt + 4 * g);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int query = 16 * qt + 4 * g + r;
-                    const bool ok = key < L && query < L && !(causal && key > query);
-                    const float pr = ok ? __builtin_amdgcn_exp2f(a[r] * sc2 - ls[r]) : 0.f;
-                    a[r] = pr;
-                    e[r] = pr * (e[r] - dl[r]) * scale;
-                }
-                pt[hh] = a;
-                dst[hh] = e;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            const bf16x8 pf = pack_pair(pt[0], pt[1]);
-            const bf16x8 df = pack_pair(dst[0], dst[1]);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                dv[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_tr_frag(R1, sp, dt, g, q, p), pf, dv[dt], 0, 0, 0);
-                dk[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_tr_frag(R0, sp, dt, g, q, p), df, dk[dt], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        at_store_tile(dbase + d, ld3, L, 16 * kt, dk, 1.0f, lane);
-        at_store_tile(dbase + 2 * d, ld3, L, 16 * kt, dv, 1.0f, lane);
-    }
-}
-
-// Backward with ALL FOUR operands of a (sample, head) resident in LDS (round 3).  PMC on the two-image kernel above
-// (profiles/r03_pmc_attention.txt): FETCH_SIZE = 2.0x the algorithmic reads -- Q, K, V and dO each travel from the fabric TWICE
-// (once as a wave's fragments, once as the staged image of the other phase), because the eight (sample, head) blocks a CU
-// keeps in flight per XCD-L2 share outlive a 4-MiB L2 -- and with the dqkv write the kernel moves 3.45 GB in 578 us = 6.0 TB/s:
-// it IS bandwidth-bound, on traffic it does not need.  Here every operand is read once (8 x 16 B per thread, all in flight
-// together), both phases take their fragments from the LDS images, and one barrier separates them.  Costs twice the LDS per
-// block (4 x LP x 128 B: 32.5 KiB at LP = 64), so fewer blocks per CU, each with all of its loads in flight at once.
+// Backward with ALL FOUR operands of a (sample, head) resident in LDS: every operand is read from memory once (8 x 16 B per
+// thread, all in flight together), both phases take their fragments from the LDS images, and one barrier separates them:
+//   A  wave = one 16-query tile: S^T, dP^T -> lse, delta, dQ
+//   B  wave = one 16-key tile:   S, dP -> dV, dK
+// Costs 4 x LP x 128 B of LDS per block (32.5 KiB at LP = 64).  It replaced (round 3) a backward that kept two images -- K, V in
+// phase A, then Q, dO restaged over them for phase B -- and took the other pair of each phase as per-wave fragments from memory.
+// PMC on that kernel (profiles/r03_pmc_attention.txt): FETCH_SIZE = 2.0x the algorithmic reads -- Q, K, V and dO each travelled
+// from the fabric TWICE, because the eight (sample, head) blocks a CU keeps in flight per XCD-L2 share outlive a 4-MiB L2 -- and
+// with the dqkv write it moved 3.45 GB in 578 us = 6.0 TB/s: bandwidth-bound, on traffic it did not need.
 // Round 4: templated on the causal flag, and the arithmetic of both phases cut down (the kernel proved bound by its vector work,
 // not by bytes in flight -- a prefetching persistent form was slower, profiles/r04_attention_long.txt): fragment addresses are
 // per-lane constants + immediates; key masks only in the one tile that holds rows behind L (and the diagonal tile of a causal
@@ -562,7 +439,7 @@ __global__ __launch_bounds__((NT <= 8 ? 64 * NT : 32 * (NT + 1)), AT_MINW(NT)) v
 // PACKED: the items are variable-length sequences of a packed batch (cu_rows), which may use fewer than NT tiles; a dense batch
 // always uses all NT and needs no tile guards.
 template <int NT, bool CAUSAL, bool PACKED>
-__global__ __launch_bounds__((NT <= 8 ? 64 * NT : 32 * (NT + 1)), AT_MINW(NT)) void attn_bf16_bwd4_kernel(
+__global__ __launch_bounds__(64 * NT, AT_MINW(NT)) void attn_bf16_bwd4_kernel(
     int L, int heads, const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
     bf16_t* __restrict__ dqkv, const int* __restrict__ seq_ids, const int* __restrict__ cu_rows) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -607,7 +484,7 @@ __global__ __launch_bounds__((NT <= 8 ? 64 * NT : 32 * (NT + 1)), AT_MINW(NT)) v
             for (int u = 0; u < U; ++u) {
                 const int id = base + u * step, row = id >> 3, ch = id & 7;
                 if (id < total) {
-                    const int off = at_off(row, ch);
+                    const int off = at_off<AT_ROWB>(row, ch);
                     *reinterpret_cast<uint4*>(Kl + off) = v[u][0];
                     *reinterpret_cast<uint4*>(Vl + off) = v[u][1];
                     *reinterpret_cast<uint4*>(Ql + off) = v[u][2];
@@ -629,10 +506,10 @@ __global__ __launch_bounds__((NT <= 8 ? 64 * NT : 32 * (NT + 1)), AT_MINW(NT)) v
     const int nt_used = PACKED ? (L + 15) >> 4 : NT;
     const bool ragged = (L & 15) != 0;                       // the last tile holds rows behind L
     // fragment offsets of tile 0 / slice 0: tiles are 2 KiB apart, the swizzle only depends on the row inside the tile
-    const int kq0 = at_off(c, g), kq1 = at_off(c, 4 + g);
+    const int kq0 = at_off<AT_ROWB>(c, g), kq1 = at_off<AT_ROWB>(c, 4 + g);
     int vt[4];
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) vt[dt] = at_off(4 * g + q, 2 * dt + (p >> 1)) + (p & 1) * 8;
+    for (int dt = 0; dt < 4; ++dt) vt[dt] = at_off<AT_ROWB>(4 * g + q, 2 * dt + (p >> 1)) + (p & 1) * 8;
 
     // ---- phase A: wave = one 16-query tile: S^T, dP^T -> lse, delta, dQ
     for (int qt = wave; qt < nt_used; qt += nwaves) {
@@ -712,7 +589,7 @@ __global__ __launch_bounds__((NT <= 8 ? 64 * NT : 32 * (NT + 1)), AT_MINW(NT)) v
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        at_store_tile(dbase, ld3, L, 16 * qt, dq, 1.0f, lane);
+        at_store_tile<AT_HD>(dbase, ld3, L, 16 * qt, dq, 1.0f, lane);
     }
     __syncthreads();                           // -lse / -delta * scale of every query tile are complete
 
@@ -774,8 +651,8 @@ __global__ __launch_bounds__((NT <= 8 ? 64 * NT : 32 * (NT + 1)), AT_MINW(NT)) v
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        at_store_tile(dbase + d, ld3, L, 16 * kt, dk, 1.0f, lane);
-        at_store_tile(dbase + 2 * d, ld3, L, 16 * kt, dv, 1.0f, lane);
+        at_store_tile<AT_HD>(dbase + d, ld3, L, 16 * kt, dk, 1.0f, lane);
+        at_store_tile<AT_HD>(dbase + 2 * d, ld3, L, 16 * kt, dv, 1.0f, lane);
     }
 }
 
@@ -783,129 +660,32 @@ __global__ __launch_bounds__((NT <= 8 ? 64 * NT : 32 * (NT + 1)), AT_MINW(NT)) v
 // Same data flow as above (whole K, V of one (sample, head) in LDS, one block of up to 16 waves per CU), but a query
 // tile's scores no longer fit registers, so the softmax runs ONLINE over chunks of key tiles: running row maximum m,
 // rescaled row sum l and rescaled accumulators, as in flash attention.  Templated on the head dim:
-//   HD = 64: 128-byte LDS rows, 224 < L <= 608 (ViT-L/14-336: 577 tokens; 2 x 608 x 128 B = 152 KiB);
-//   HD = 80: rows padded to 128 elements = 256 bytes (dims 80..127 zero), three 32-deep k-slices, five 16-column output
-//            tiles, L <= 288 (ViT-H/14: 257 tokens; 2 x 288 x 256 B = 144 KiB).
-// Backward phase A makes two sweeps over the keys: sweep 1 gets log-sum-exp and delta = sum_k P dP with the same online
-// rescaling (so the forward output is not needed), sweep 2 recomputes S, dP chunk-wise for dS and dQ; phase B is the
-// short kernel's (it already walks the query tiles pairwise).
+//   HD = 64: 128 < L <= 608 (ViT-B/16: 197 tokens; ViT-L/14-336: 577 tokens; 2 x 608 x 128 B = 152 KiB);
+//   HD = 80: L <= 288 (ViT-H/14: 257 tokens; 2 x 288 x 256 B = 144 KiB).
+// Backward: two phases that reuse the same two LDS images (so a (sample, head) needs 2 x LP x ROWB, and each phase's registers
+// are dead in the other):
+//   A  K, V in LDS; wave = one 16-query tile (Q, dO fragments straight from memory): S^T, dP^T -> lse, delta, dQ
+//   B  Q, dO in LDS; wave = one 16-key tile (K, V fragments from memory, L2-warm), query tiles walked in pairs: S, dP -> dV, dK
+// Phase A makes two sweeps over the keys: sweep 1 gets log-sum-exp and delta = sum_k P dP with the same online rescaling (so
+// the forward output is not needed), sweep 2 recomputes S, dP chunk-wise for dS and dQ.
 #define ATL_CH 8      // key tiles per chunk (forward)
-#ifndef ATL_LSUM_MFMA
-#define ATL_LSUM_MFMA 1   // 1: the forward's softmax denominator as an all-ones MFMA tile (experiment)
-#endif
 #define ATL_CHB 4     // backward phase A keeps S and dP of a chunk: half the chunk to stay within 128 VGPRs at 16 waves
 
-template <int HD> struct AtlCfg {
-    static constexpr int ROWB = HD <= 64 ? 128 : 256;      // LDS row bytes
-    static constexpr int KS = (HD + 31) / 32;              // 32-deep k-slices of the QK^T reduction
-    static constexpr int DT = (HD + 15) / 16;              // 16-column tiles of the head dim
-    static constexpr int CHUNKS = HD / 8;                  // valid 16-byte chunks per row
-    static constexpr int MAXW_F = HD <= 64 ? 16 : 12;      // waves per block, forward (head dim 80 with the fast path: > 128 VGPRs)
-    static constexpr int MAXW_B = HD <= 64 ? 16 : 12;      // backward: head dim 80 needs 168 VGPRs -> three waves per SIMD
-};
-// Swizzle of the 16-byte chunks of a row.  A 16-lane group of ds_read_b128 (rows c, chunk 4ks+g) and a 32-lane group of
-// ds_read_b64_tr_b16 (eight consecutive rows, 32 bytes each) must land on 256 distinct bytes of the 64 banks:
-//   128-byte rows: odd rows already sit in the other half of the banks; xor with 2 * ((row >> 1) & 3) inside the 8 chunks
-//   256-byte rows: every row starts on bank 0, so the xor needs three row bits: 2 * (row & 7) inside the 16 chunks
-//                  (with the 128-byte rule rows 2i and 2i+1 collided: every fragment read of the head-dim-80 kernels 2-way)
-template <int ROWB>
-__device__ __forceinline__ int atl_off(int row, int chunk) {
-    if constexpr (ROWB == 256) return row * ROWB + ((chunk ^ ((row & 7) << 1)) << 4);
-    return row * ROWB + ((chunk ^ (((row >> 1) & 3) << 1)) << 4);
-}
-// two operands at once, loads first (see at_stage2)
-template <int HD>
-__device__ __forceinline__ void atl_stage2(char* ldsA, const bf16_t* srcA, long ldA, char* ldsB, const bf16_t* srcB, long ldB,
-                                           int L, int LP) {
-    // U x 2 loads in flight per thread: with a full block (16 x 64 threads at head dim 64, 12 x 64 at 80) ONE batch covers both
-    // operand images, i.e. one HBM round trip per staging instead of two or three (nothing else runs on the CU meanwhile: the
-    // images of one (sample, head) fill its LDS)
-    constexpr int RC = AtlCfg<HD>::ROWB / 16, U = HD <= 64 ? 5 : 6;
-    const int total = LP * RC, step = blockDim.x;
-    for (int base = threadIdx.x; base < total; base += U * step) {
-        uint4 va[U], vb[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int id = base + u * step, row = id / RC, ch = id % RC;
-            va[u] = make_uint4(0u, 0u, 0u, 0u);
-            vb[u] = make_uint4(0u, 0u, 0u, 0u);
-            if (id < total && row < L && ch < AtlCfg<HD>::CHUNKS) {
-                va[u] = *reinterpret_cast<const uint4*>(srcA + (long)row * ldA + ch * 8);
-                vb[u] = *reinterpret_cast<const uint4*>(srcB + (long)row * ldB + ch * 8);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int id = base + u * step, row = id / RC, ch = id % RC;
-            if (id < total) {
-                *reinterpret_cast<uint4*>(ldsA + atl_off<AtlCfg<HD>::ROWB>(row, ch)) = va[u];
-                *reinterpret_cast<uint4*>(ldsB + atl_off<AtlCfg<HD>::ROWB>(row, ch)) = vb[u];
-            }
-        }
-    }
-}
-template <int HD>
-__device__ __forceinline__ bf16x8 atl_row_frag(const char* img, int tile, int ks, int g, int c) {
-    return lds_read8(img + atl_off<AtlCfg<HD>::ROWB>(16 * tile + c, 4 * ks + g));
-}
-template <int HD>
-__device__ __forceinline__ bf16x8 atl_tr_frag(const char* img, int s, int dt, int g, int q, int p) {
-    const int r0 = 32 * s + 4 * g + q, r1 = r0 + 16;
-    const int ch = 2 * dt + (p >> 1), hb = (p & 1) * 8;
-    return lds_tr8(img + atl_off<AtlCfg<HD>::ROWB>(r0, ch) + hb, img + atl_off<AtlCfg<HD>::ROWB>(r1, ch) + hb);
-}
-template <int HD>
-__device__ __forceinline__ bf16x8 atl_global_frag(const bf16_t* src, long ld, int L, int tile, int ks, int g, int c) {
-    const int row = 16 * tile + c, ch = 4 * ks + g;
-    uint4 v = make_uint4(0u, 0u, 0u, 0u);
-    if (row < L && ch < AtlCfg<HD>::CHUNKS) v = *reinterpret_cast<const uint4*>(src + (long)row * ld + ch * 8);
-    union { uint4 u; bf16x8 f; } x;
-    x.u = v;
-    return x.f;
-}
-// 16 rows x HD columns: the first four 16-column tiles through the coalesced path, a fifth (HD = 80) with 8-byte stores
-template <int HD>
-__device__ __forceinline__ void atl_store_tile(bf16_t* dst, long ld, int L, int row0, const f32x4 (&o)[AtlCfg<HD>::DT], float mul,
-                                               int lane) {
-    const f32x4 o4[4] = {o[0], o[1], o[2], o[3]};
-    at_store_tile(dst, ld, L, row0, o4, mul, lane);
-    if constexpr (AtlCfg<HD>::DT > 4) {
-        const int g = lane >> 4, c = lane & 15;
-        if (row0 + c < L)
-            store4(dst + (long)(row0 + c) * ld + 64 + 4 * g, make_float4(o[4][0] * mul, o[4][1] * mul, o[4][2] * mul, o[4][3] * mul));
-    }
-}
 __device__ __forceinline__ int atl_lp(int L) { return ((L + 31) >> 5) << 5; }
 
-#ifdef ATL_PROFILE
-// diagnostic build only (-DATL_PROFILE): per-wave cycle sums of the long forward: [0] whole wave [1] staging + barrier
-// [2] the query-tile loop without its stores [3] stores [4] waves counted
-__device__ unsigned long long g_atl_dbg[8];
-extern "C" int clipx_debug_atl(unsigned long long* out, int reset) {
-    if (reset) { unsigned long long z[8] = {0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_atl_dbg), z, sizeof(z)); }
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_atl_dbg), 8 * sizeof(unsigned long long));
-}
-#endif
 template <int HD, bool CAUSAL>
-__global__ __launch_bounds__(AtlCfg<HD>::MAXW_F * 64) void attn_bf16_long_fwd_kernel(int L, int heads, const bf16_t* __restrict__ qkv,
+__global__ __launch_bounds__(AtCfg<HD>::MAXW_F * 64) void attn_bf16_long_fwd_kernel(int L, int heads, const bf16_t* __restrict__ qkv,
                                                                   bf16_t* __restrict__ out, float* __restrict__ lse_out) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int ROWB = AtlCfg<HD>::ROWB, KS = AtlCfg<HD>::KS, DT = AtlCfg<HD>::DT;
+    constexpr int ROWB = AtCfg<HD>::ROWB, KS = AtCfg<HD>::KS, DT = AtCfg<HD>::DT;
     const int LP = atl_lp(L);
     char* Ks = smem;
     char* Vs = smem + LP * ROWB;
     const int b = blockIdx.x / heads, h = blockIdx.x % heads;
     const int d = heads * HD;
     const bf16_t* base = qkv + (long)b * L * 3 * d + h * HD;
-#ifdef ATL_PROFILE
-    const long t_begin = clock64();
-    long t_store = 0;
-#endif
-    atl_stage2<HD>(Ks, base + d, 3 * d, Vs, base + 2 * d, 3 * d, L, LP);
+    at_stage2<HD, AtCfg<HD>::STAGE_U>(Ks, base + d, 3 * d, Vs, base + 2 * d, 3 * d, L, LP);
     __syncthreads();
-#ifdef ATL_PROFILE
-    const long t_staged = clock64();
-#endif
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nwaves = blockDim.x >> 6;
@@ -915,9 +695,9 @@ __global__ __launch_bounds__(AtlCfg<HD>::MAXW_F * 64) void attn_bf16_long_fwd_ke
     // per-lane byte offsets of the fragments of key tile 0 / key slice 0 (the swizzle is periodic in 8 rows, tiles are 16)
     int kq[KS], vt0[DT];          // (the transposed fragment's second half sits 16 rows further: same swizzle, + 16 * ROWB)
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) kq[ks] = atl_off<ROWB>(c, 4 * ks + g);
+    for (int ks = 0; ks < KS; ++ks) kq[ks] = at_off<ROWB>(c, 4 * ks + g);
 #pragma unroll
-    for (int dt = 0; dt < DT; ++dt) vt0[dt] = atl_off<ROWB>(4 * g + q, 2 * dt + (p >> 1)) + (p & 1) * 8;
+    for (int dt = 0; dt < DT; ++dt) vt0[dt] = at_off<ROWB>(4 * g + q, 2 * dt + (p >> 1)) + (p & 1) * 8;
     // all-ones A fragment: o-style MFMA of it with the packed probabilities = their column sums, i.e. the softmax denominator
     // of the lane's query in every output row -- the 32 row-sum adds per chunk leave the vector pipe, which is what bounds this
     // loop (per 128-key chunk and wave: 32 v_exp_f32 at quarter rate = 512 issue cycles + ~100 full-rate instructions, against
@@ -929,44 +709,29 @@ __global__ __launch_bounds__(AtlCfg<HD>::MAXW_F * 64) void attn_bf16_long_fwd_ke
         const int query = 16 * qt + c;
         bf16x8 qf[KS];
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) qf[ks] = atl_global_frag<HD>(base, 3 * d, L, qt, ks, g, c);
+        for (int ks = 0; ks < KS; ++ks) qf[ks] = at_global_frag<HD>(base, 3 * d, L, qt, ks, g, c);
         float m2 = -INFINITY;
         f32x4 o[DT], lsum = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        // One chunk of up to eight key tiles WITHOUT causal masks.  FULL: all eight exist and hold real keys only -- no guards,
-        // the scale folded into the exponent's (packed) FMA, accumulators started inside the first MFMA, fragment addresses =
-        // per-lane constants + immediates.  Otherwise `jn` tiles exist (wave-uniform guards skip the others' MFMAs, maxima and
-        // exponentials: L = 16 k + 1 puts ONE key into the last chunk of the ViT shapes) and the last of them may hold rows
-        // behind L, which get -inf.
+        // One full chunk of eight key tiles that hold real, unmasked keys only: no guards, the scale folded into the exponent's
+        // (packed) FMA, accumulators started inside the first MFMA, fragment addresses = per-lane constants + immediates.
         auto chunk = [&](int pc) {
-            constexpr bool FULL = true;
-            constexpr int jn = ATL_CH;
-            constexpr bool partial = false;
             const char* Kc = Ks + pc * 32 * ROWB;
             const char* Vc = Vs + pc * 32 * ROWB;
             f32x4 s[ATL_CH];
 #pragma unroll
             for (int j = 0; j < ATL_CH; ++j) {
-                s[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                if (FULL || j < jn) {
-                    f32x4 a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_read8(Kc + j * 16 * ROWB + kq[0]), qf[0],
-                                                                      (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                f32x4 a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_read8(Kc + j * 16 * ROWB + kq[0]), qf[0],
+                                                                  (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
 #pragma unroll
-                    for (int ks = 1; ks < KS; ++ks)
-                        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_read8(Kc + j * 16 * ROWB + kq[ks]), qf[ks], a, 0, 0, 0);
-                    if (!FULL && partial && j == jn - 1) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            if (32 * pc + 16 * j + 4 * g + r >= L) a[r] = -INFINITY;
-                    }
-                    s[j] = a;
-                }
+                for (int ks = 1; ks < KS; ++ks)
+                    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_read8(Kc + j * 16 * ROWB + kq[ks]), qf[ks], a, 0, 0, 0);
+                s[j] = a;
             }
-            float cm = fmaxf(fmaxf(s[0][0], s[0][1]), fmaxf(s[0][2], s[0][3]));          // tile 0 of a chunk always exists
+            float cm = fmaxf(fmaxf(s[0][0], s[0][1]), fmaxf(s[0][2], s[0][3]));
 #pragma unroll
-            for (int j = 1; j < ATL_CH; ++j)
-                if (FULL || j < jn) cm = fmaxf(fmaxf(cm, fmaxf(s[j][0], s[j][1])), fmaxf(s[j][2], s[j][3]));
+            for (int j = 1; j < ATL_CH; ++j) cm = fmaxf(fmaxf(cm, fmaxf(s[j][0], s[j][1])), fmaxf(s[j][2], s[j][3]));
             cm = group_max(cm);
             const float mn = fmaxf(m2, cm * sc2);                  // finite: key 32 pc is real
             const float alpha = __builtin_amdgcn_exp2f(m2 - mn);
@@ -976,29 +741,21 @@ __global__ __launch_bounds__(AtlCfg<HD>::MAXW_F * 64) void attn_bf16_long_fwd_ke
             const f32x2 sc22 = {sc2, sc2}, nmn2 = {-mn, -mn};
 #pragma unroll
             for (int j = 0; j < ATL_CH; ++j)
-                if (FULL || j < jn) {
 #pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const f32x2 t = __builtin_elementwise_fma((f32x2){s[j][2 * h], s[j][2 * h + 1]}, sc22, nmn2);   // v_pk_fma_f32
-                        s[j][2 * h] = __builtin_amdgcn_exp2f(t[0]);
-                        s[j][2 * h + 1] = __builtin_amdgcn_exp2f(t[1]);
-#if !ATL_LSUM_MFMA
-                        lsum[0] += s[j][2 * h] + s[j][2 * h + 1];
-#endif
-                    }
+                for (int h = 0; h < 2; ++h) {
+                    const f32x2 t = __builtin_elementwise_fma((f32x2){s[j][2 * h], s[j][2 * h + 1]}, sc22, nmn2);   // v_pk_fma_f32
+                    s[j][2 * h] = __builtin_amdgcn_exp2f(t[0]);
+                    s[j][2 * h + 1] = __builtin_amdgcn_exp2f(t[1]);
                 }
 #pragma unroll
-            for (int jp = 0; jp < ATL_CH / 2; ++jp)
-                if (FULL || 2 * jp < jn) {
-                    const bf16x8 pf = pack_pair(s[2 * jp], s[2 * jp + 1]);      // (a tile that does not exist: zeros)
+            for (int jp = 0; jp < ATL_CH / 2; ++jp) {
+                const bf16x8 pf = pack_pair(s[2 * jp], s[2 * jp + 1]);
 #pragma unroll
-                    for (int dt = 0; dt < DT; ++dt)
-                        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                            lds_tr8(Vc + jp * 32 * ROWB + vt0[dt], Vc + (jp * 32 + 16) * ROWB + vt0[dt]), pf, o[dt], 0, 0, 0);
-#if ATL_LSUM_MFMA
-                    lsum = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf, lsum, 0, 0, 0);
-#endif
-                }
+                for (int dt = 0; dt < DT; ++dt)
+                    o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        lds_tr8(Vc + jp * 32 * ROWB + vt0[dt], Vc + (jp * 32 + 16) * ROWB + vt0[dt]), pf, o[dt], 0, 0, 0);
+                lsum = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf, lsum, 0, 0, 0);
+            }
             m2 = mn;
         };
         for (int pc = 0; pc < np; pc += ATL_CH / 2) {
@@ -1047,17 +804,12 @@ __global__ __launch_bounds__(AtlCfg<HD>::MAXW_F * 64) void attn_bf16_long_fwd_ke
                             const f32x2 t = __builtin_elementwise_fma((f32x2){s2[j][2 * h], s2[j][2 * h + 1]}, sc22, nmn2);
                             s2[j][2 * h] = __builtin_amdgcn_exp2f(t[0]);
                             s2[j][2 * h + 1] = __builtin_amdgcn_exp2f(t[1]);
-#if !ATL_LSUM_MFMA
-                            lsum[0] += s2[j][2 * h] + s2[j][2 * h + 1];
-#endif
                         }
                     const bf16x8 pf = pack_pair(s2[0], s2[1]);
 #pragma unroll
                     for (int dt = 0; dt < DT; ++dt)
                         o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_tr8(Vc + vt0[dt], Vc + 16 * ROWB + vt0[dt]), pf, o[dt], 0, 0, 0);
-#if ATL_LSUM_MFMA
                     lsum = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf, lsum, 0, 0, 0);
-#endif
                     m2 = mn;
                 }
                 break;
@@ -1072,7 +824,7 @@ __global__ __launch_bounds__(AtlCfg<HD>::MAXW_F * 64) void attn_bf16_long_fwd_ke
                 if (kt < nt) {
 #pragma unroll
                     for (int ks = 0; ks < KS; ++ks)
-                        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(atl_row_frag<HD>(Ks, kt, ks, g, c), qf[ks], a, 0, 0, 0);
+                        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_row_frag<HD>(Ks, kt, ks, g, c), qf[ks], a, 0, 0, 0);
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -1094,9 +846,6 @@ __global__ __launch_bounds__(AtlCfg<HD>::MAXW_F * 64) void attn_bf16_long_fwd_ke
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     s[j][r] = __builtin_amdgcn_exp2f(s[j][r] - mn);
-#if !ATL_LSUM_MFMA
-                    lsum[0] += s[j][r];
-#endif
                 }
 #pragma unroll
             for (int jp = 0; jp < ATL_CH / 2; ++jp) {
@@ -1105,41 +854,19 @@ __global__ __launch_bounds__(AtlCfg<HD>::MAXW_F * 64) void attn_bf16_long_fwd_ke
                     const bf16x8 pf = pack_pair(s[2 * jp], s[2 * jp + 1]);
 #pragma unroll
                     for (int dt = 0; dt < DT; ++dt)
-                        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(atl_tr_frag<HD>(Vs, sp, dt, g, q, p), pf, o[dt], 0, 0, 0);
-#if ATL_LSUM_MFMA
+                        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_tr_frag<HD>(Vs, sp, dt, g, q, p), pf, o[dt], 0, 0, 0);
                     lsum = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf, lsum, 0, 0, 0);
-#endif
                 }
             }
             m2 = mn;
             }
         }
-#if ATL_LSUM_MFMA
         const float l = lsum[0];                                  // every output row of the ones tile holds the query's sum
-#else
-        const float l = group_sum(lsum[0]);
-#endif
-#ifdef ATL_PROFILE
-        const long ts0 = clock64();
-#endif
-        atl_store_tile<HD>(out + (long)b * L * d + h * HD, d, L, 16 * qt, o, 1.0f / l, lane);
-#ifdef ATL_PROFILE
-        t_store += clock64() - ts0;
-#endif
+        at_store_tile<HD>(out + (long)b * L * d + h * HD, d, L, 16 * qt, o, 1.0f / l, lane);
         // log-sum-exp of the scaled scores in the log2 domain (what the backward's P = exp2(s - lse) needs): kept by callers that
         // will run clipx_attention_bwd_lse, whose phase A then needs no sweep of its own for it
         if (lse_out != nullptr && g == 0 && query < L) lse_out[(long)blockIdx.x * L + query] = m2 + log2f(l);
     }
-#ifdef ATL_PROFILE
-    if (lane == 0 && (blockIdx.x & 15) == 0) {          // a sample of the blocks: the atomics themselves must not load the L2
-        const long t_end = clock64();
-        atomicAdd(&g_atl_dbg[0], (unsigned long long)(t_end - t_begin));
-        atomicAdd(&g_atl_dbg[1], (unsigned long long)(t_staged - t_begin));
-        atomicAdd(&g_atl_dbg[2], (unsigned long long)(t_end - t_staged - t_store));
-        atomicAdd(&g_atl_dbg[3], (unsigned long long)t_store);
-        atomicAdd(&g_atl_dbg[4], 1ull);
-    }
-#endif
 }
 
 // FAST = the forward handed over its log-sum-exp and output, no causal mask (every vision tower): no per-score masks at all --
@@ -1147,11 +874,11 @@ __global__ __launch_bounds__(AtlCfg<HD>::MAXW_F * 64) void attn_bf16_long_fwd_ke
 // tile that holds them -- scale and subtraction folded into packed FMAs (-lse and -delta * scale are what phase A leaves in
 // LDS), fragment addresses = per-lane constants + immediates.  Was ~13 vector instructions per score and phase, is ~6.
 template <int HD, bool HAVE_LSE, bool CAUSAL>
-__global__ __launch_bounds__(AtlCfg<HD>::MAXW_B * 64) void attn_bf16_long_bwd_kernel(int L, int heads, const bf16_t* __restrict__ qkv,
+__global__ __launch_bounds__(AtCfg<HD>::MAXW_B * 64) void attn_bf16_long_bwd_kernel(int L, int heads, const bf16_t* __restrict__ qkv,
                                                                   const bf16_t* __restrict__ dout, bf16_t* __restrict__ dqkv,
                                                                   const bf16_t* __restrict__ fwd_out, const float* __restrict__ lse_in) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int ROWB = AtlCfg<HD>::ROWB, KS = AtlCfg<HD>::KS, DT = AtlCfg<HD>::DT;
+    constexpr int ROWB = AtCfg<HD>::ROWB, KS = AtCfg<HD>::KS, DT = AtCfg<HD>::DT;
     const int LP = atl_lp(L);
     char* R0 = smem;                          // phase A: K      phase B: Q
     char* R1 = smem + LP * ROWB;              // phase A: V      phase B: dO
@@ -1163,7 +890,7 @@ __global__ __launch_bounds__(AtlCfg<HD>::MAXW_B * 64) void attn_bf16_long_bwd_ke
     const bf16_t* qbase = qkv + (long)b * L * ld3 + h * HD;
     const bf16_t* gbase = dout + (long)b * L * d + h * HD;
     bf16_t* dbase = dqkv + (long)b * L * ld3 + h * HD;
-    atl_stage2<HD>(R0, qbase + d, ld3, R1, qbase + 2 * d, ld3, L, LP);
+    at_stage2<HD, AtCfg<HD>::STAGE_U>(R0, qbase + d, ld3, R1, qbase + 2 * d, ld3, L, LP);
     constexpr bool FAST = HAVE_LSE && !CAUSAL;
     constexpr bool causal = CAUSAL;
     for (int i = threadIdx.x; i < LP; i += blockDim.x) { lse2[i] = FAST ? -1e30f : 1e30f; delta[i] = 0.f; }
@@ -1178,9 +905,9 @@ __global__ __launch_bounds__(AtlCfg<HD>::MAXW_B * 64) void attn_bf16_long_bwd_ke
     // per-lane byte offsets of the fragments of tile 0 / slice 0 (as in the forward)
     int kq[KS], vt0[DT];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) kq[ks] = atl_off<ROWB>(c, 4 * ks + g);
+    for (int ks = 0; ks < KS; ++ks) kq[ks] = at_off<ROWB>(c, 4 * ks + g);
 #pragma unroll
-    for (int dt = 0; dt < DT; ++dt) vt0[dt] = atl_off<ROWB>(4 * g + q, 2 * dt + (p >> 1)) + (p & 1) * 8;
+    for (int dt = 0; dt < DT; ++dt) vt0[dt] = at_off<ROWB>(4 * g + q, 2 * dt + (p >> 1)) + (p & 1) * 8;
     const f32x2 sc22 = {sc2, sc2}, scale2 = {scale, scale};
 
     // S^T and dP^T of one chunk of key tiles against the wave's query tile; masked scores -> -inf
@@ -1192,8 +919,8 @@ __global__ __launch_bounds__(AtlCfg<HD>::MAXW_B * 64) void attn_bf16_long_bwd_ke
             if (kt < nt) {
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) {
-                    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(atl_row_frag<HD>(R0, kt, ks, g, c), qf[ks], a, 0, 0, 0);
-                    dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(atl_row_frag<HD>(R1, kt, ks, g, c), gf[ks], dp, 0, 0, 0);
+                    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_row_frag<HD>(R0, kt, ks, g, c), qf[ks], a, 0, 0, 0);
+                    dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_row_frag<HD>(R1, kt, ks, g, c), gf[ks], dp, 0, 0, 0);
                 }
             }
 #pragma unroll
@@ -1213,8 +940,8 @@ __global__ __launch_bounds__(AtlCfg<HD>::MAXW_B * 64) void attn_bf16_long_bwd_ke
         bf16x8 qf[KS], gf[KS];
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            qf[ks] = atl_global_frag<HD>(qbase, ld3, L, qt, ks, g, c);
-            gf[ks] = atl_global_frag<HD>(gbase, d, L, qt, ks, g, c);
+            qf[ks] = at_global_frag<HD>(qbase, ld3, L, qt, ks, g, c);
+            gf[ks] = at_global_frag<HD>(gbase, d, L, qt, ks, g, c);
         }
         float ls, dl;
         if constexpr (HAVE_LSE) {
@@ -1223,7 +950,7 @@ __global__ __launch_bounds__(AtlCfg<HD>::MAXW_B * 64) void attn_bf16_long_bwd_ke
             float part = 0.f;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                const bf16x8 of = atl_global_frag<HD>(fwd_out + (long)b * L * d + h * HD, d, L, qt, ks, g, c);
+                const bf16x8 of = at_global_frag<HD>(fwd_out + (long)b * L * d + h * HD, d, L, qt, ks, g, c);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) part += (float)gf[ks][k] * (float)of[k];
             }
@@ -1334,14 +1061,14 @@ __global__ __launch_bounds__(AtlCfg<HD>::MAXW_B * 64) void attn_bf16_long_bwd_ke
                     const bf16x8 df = pack_pair(s[2 * jp], s[2 * jp + 1]);
 #pragma unroll
                     for (int dt = 0; dt < DT; ++dt)
-                        dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(atl_tr_frag<HD>(R0, sp, dt, g, q, p), df, dq[dt], 0, 0, 0);
+                        dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_tr_frag<HD>(R0, sp, dt, g, q, p), df, dq[dt], 0, 0, 0);
                 }
             }
         }
-        atl_store_tile<HD>(dbase, ld3, L, 16 * qt, dq, 1.0f, lane);
+        at_store_tile<HD>(dbase, ld3, L, 16 * qt, dq, 1.0f, lane);
     }
     __syncthreads();
-    atl_stage2<HD>(R0, qbase, ld3, R1, gbase, d, L, LP);     // Q, dO
+    at_stage2<HD, AtCfg<HD>::STAGE_U>(R0, qbase, ld3, R1, gbase, d, L, LP);     // Q, dO
     __syncthreads();
 
     // ---- phase B: wave = one 16-key tile, query tiles walked in pairs
@@ -1350,8 +1077,8 @@ __global__ __launch_bounds__(AtlCfg<HD>::MAXW_B * 64) void attn_bf16_long_bwd_ke
         bf16x8 kf[KS], vf[KS];
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            kf[ks] = atl_global_frag<HD>(qbase + d, ld3, L, kt, ks, g, c);
-            vf[ks] = atl_global_frag<HD>(qbase + 2 * d, ld3, L, kt, ks, g, c);
+            kf[ks] = at_global_frag<HD>(qbase + d, ld3, L, kt, ks, g, c);
+            vf[ks] = at_global_frag<HD>(qbase + 2 * d, ld3, L, kt, ks, g, c);
         }
         f32x4 dv[DT], dk[DT];
 #pragma unroll
@@ -1408,8 +1135,8 @@ __global__ __launch_bounds__(AtlCfg<HD>::MAXW_B * 64) void attn_bf16_long_bwd_ke
                 f32x4 a = {0.f, 0.f, 0.f, 0.f}, e = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) {
-                    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(atl_row_frag<HD>(R0, qt, ks, g, c), kf[ks], a, 0, 0, 0);
-                    e = __builtin_amdgcn_mfma_f32_16x16x32_bf16(atl_row_frag<HD>(R1, qt, ks, g, c), vf[ks], e, 0, 0, 0);
+                    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_row_frag<HD>(R0, qt, ks, g, c), kf[ks], a, 0, 0, 0);
+                    e = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_row_frag<HD>(R1, qt, ks, g, c), vf[ks], e, 0, 0, 0);
                 }
                 const f32x4 ls = *reinterpret_cast<const f32x4*>(lse2 + 16 * qt + 4 * g);
                 const f32x4 dl = *reinterpret_cast<const f32x4*>(delta + 16 * qt + 4 * g);
@@ -1428,14 +1155,33 @@ __global__ __launch_bounds__(AtlCfg<HD>::MAXW_B * 64) void attn_bf16_long_bwd_ke
             const bf16x8 df = pack_pair(dst[0], dst[1]);
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {
-                dv[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(atl_tr_frag<HD>(R1, sp, dt, g, q, p), pf, dv[dt], 0, 0, 0);
-                dk[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(atl_tr_frag<HD>(R0, sp, dt, g, q, p), df, dk[dt], 0, 0, 0);
+                dv[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_tr_frag<HD>(R1, sp, dt, g, q, p), pf, dv[dt], 0, 0, 0);
+                dk[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_tr_frag<HD>(R0, sp, dt, g, q, p), df, dk[dt], 0, 0, 0);
             }
         }
         }
-        atl_store_tile<HD>(dbase + d, ld3, L, 16 * kt, dk, 1.0f, lane);
-        atl_store_tile<HD>(dbase + 2 * d, ld3, L, 16 * kt, dv, 1.0f, lane);
+        at_store_tile<HD>(dbase + d, ld3, L, 16 * kt, dk, 1.0f, lane);
+        at_store_tile<HD>(dbase + 2 * d, ld3, L, 16 * kt, dv, 1.0f, lane);
     }
+}
+
+// ---- launches
+// runtime bools -> std::bool_constant arguments of a generic lambda: one kernel instantiation per combination
+template <typename F>
+static void with_bools(F&& f) { f(); }
+template <typename F, typename... Rest>
+static void with_bools(F&& f, bool b, Rest... rest) {
+    if (b) with_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+    else with_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
+// experiment switches, each read once: CLIPX_ATTN_WAVES / CLIPX_ATTN_BWD4_WAVES override the waves per block of the forward and
+// online-softmax kernels / of the four-image backward; CLIPX_ATTN_GENERIC=1 sends everything to the generic tiled kernels
+static int env_int(const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; }
+static int attn_waves_override() { static const int v = env_int("CLIPX_ATTN_WAVES"); return v; }
+static int attn_bwd4_waves_override() { static const int v = env_int("CLIPX_ATTN_BWD4_WAVES"); return v; }
+static bool attn_force_generic() {
+    static const bool v = [] { const char* e = getenv("CLIPX_ATTN_GENERIC"); return e && e[0] == '1'; }();
+    return v;
 }
 
 // largest L whose two operand images (+ lse / delta in the backward) fit the 160 KiB of LDS
@@ -1446,7 +1192,7 @@ template <int HD>
 static int launch_bf16_long(bool bwd, int batch, int L, int heads, int causal, const void* qkv, const void* dout, void* out,
                             hipStream_t stream, const void* fwd_out = nullptr, float* lse = nullptr) {
     const int LP = ((L + 31) / 32) * 32;
-    const size_t lds = (size_t)2 * LP * AtlCfg<HD>::ROWB + (bwd ? (size_t)2 * LP * sizeof(float) : 0);
+    const size_t lds = (size_t)2 * LP * AtCfg<HD>::ROWB + (bwd ? (size_t)2 * LP * sizeof(float) : 0);
     CLIPX_CHECK(lds <= 160 * 1024, "long attention: L=%d does not fit LDS", L);
     const int nt = (L + 15) / 16;
     // One block per CU when the images take more than half the LDS: as many waves as it may have (16 measured best at L = 577).
@@ -1454,111 +1200,68 @@ static int launch_bf16_long(bool bwd, int batch, int L, int heads, int causal, c
     // VGPRs allow and one block's staging runs beside the other's MFMA phase (L = 197: 8 waves 0.194 / 0.580 ms, 13 waves
     // 0.254 / 0.679, 7 waves 0.210 / 0.614 -- profiles/r03_attention_long.txt).
     int waves = 2 * lds <= 160 * 1024 ? (nt < 8 ? nt : 8) : nt;
-    {
-        static int wv = -1;
-        if (wv < 0) { const char* e = getenv("CLIPX_ATTN_WAVES"); wv = e ? atoi(e) : 0; }
-        if (wv > 0) waves = wv;
-    }
-    const int maxw = bwd ? AtlCfg<HD>::MAXW_B : AtlCfg<HD>::MAXW_F;
+    if (attn_waves_override() > 0) waves = attn_waves_override();
+    const int maxw = bwd ? AtCfg<HD>::MAXW_B : AtCfg<HD>::MAXW_F;
     if (waves > maxw) waves = maxw;
     if (waves < 1) waves = 1;
-#define ATL_BWD(LSEV, CAUSALV, OUTP, LSEP)                                                                                           \
-    do {                                                                                                                             \
-        (void)hipFuncSetAttribute((const void*)attn_bf16_long_bwd_kernel<HD, LSEV, CAUSALV>,                                         \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                            \
-        hipLaunchKernelGGL((attn_bf16_long_bwd_kernel<HD, LSEV, CAUSALV>), dim3(batch * heads), dim3(64 * waves), lds, stream, L,    \
-                           heads, (const bf16_t*)qkv, (const bf16_t*)dout, (bf16_t*)out, (const bf16_t*)(OUTP), (const float*)(LSEP)); \
-    } while (0)
-    if (bwd && fwd_out != nullptr && lse != nullptr) {
-        if (causal) ATL_BWD(true, true, fwd_out, lse);
-        else ATL_BWD(true, false, fwd_out, lse);
-    } else if (bwd) {
-        if (causal) ATL_BWD(false, true, nullptr, nullptr);
-        else ATL_BWD(false, false, nullptr, nullptr);
+    if (bwd) {
+        const bool have_lse = fwd_out != nullptr && lse != nullptr;
+        with_bools([&](auto lse_c, auto causal_c) {
+            auto kernel = attn_bf16_long_bwd_kernel<HD, decltype(lse_c)::value, decltype(causal_c)::value>;
+            (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(kernel, dim3(batch * heads), dim3(64 * waves), lds, stream, L, heads, (const bf16_t*)qkv,
+                               (const bf16_t*)dout, (bf16_t*)out, have_lse ? (const bf16_t*)fwd_out : nullptr,
+                               have_lse ? (const float*)lse : nullptr);
+        }, have_lse, causal != 0);
     } else {
-        if (causal) {
-            (void)hipFuncSetAttribute((const void*)attn_bf16_long_fwd_kernel<HD, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((attn_bf16_long_fwd_kernel<HD, true>), dim3(batch * heads), dim3(64 * waves), lds, stream, L, heads,
-                               (const bf16_t*)qkv, (bf16_t*)out, lse);
-        } else {
-            (void)hipFuncSetAttribute((const void*)attn_bf16_long_fwd_kernel<HD, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((attn_bf16_long_fwd_kernel<HD, false>), dim3(batch * heads), dim3(64 * waves), lds, stream, L, heads,
-                               (const bf16_t*)qkv, (bf16_t*)out, lse);
-        }
+        with_bools([&](auto causal_c) {
+            auto kernel = attn_bf16_long_fwd_kernel<HD, decltype(causal_c)::value>;
+            (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(kernel, dim3(batch * heads), dim3(64 * waves), lds, stream, L, heads, (const bf16_t*)qkv,
+                               (bf16_t*)out, lse);
+        }, causal != 0);
     }
-#undef ATL_BWD
     CLIPX_LAUNCH_CHECK();
     return 0;
 }
 
-// =============================================================================== C ABI
+// whole-sequence kernels: NT tiles of 16 rows, head dim 64
 template <int NT>
 static int launch_bf16(bool bwd, int batch, int L, int heads, int causal, const void* qkv, const void* dout,
                        void* out, hipStream_t stream, const int* seq_ids = nullptr, const int* cu_rows = nullptr) {
     constexpr int LP = 16 * NT;
-    const size_t lds = bwd ? (size_t)2 * LP * AT_ROWB + 2 * LP * sizeof(float) : (size_t)2 * LP * AT_ROWB;
-    // Two 16-row tiles per wave: blocks of half as many waves, so more (sample, head) blocks are resident per CU and one
-    // block's staging overlaps another's MFMA phase.  Measured at b=4096 (scripts/bench_attn.py): L=77 backward
-    // 966 -> 728 us, forward 412 -> 325 us with 3 waves instead of 5; L=50 backward 666 -> 632 us with 2 instead of 4
-    // (one wave per block is slower again).  CLIPX_ATTN_WAVES overrides the count (experiments).
     const int nt_used = (L + 15) / 16;
-    // 129..224 tokens (NT = 14, 256 VGPRs, ~57 KiB LDS): two blocks of 4 waves fill a CU's 8 wave slots; measured at
-    // L = 197 (ViT-B/16, b=512 x 12 heads): 4 waves 0.30 / 0.74 ms fwd / bwd, 7 waves 0.34 / 0.84, 3 waves 0.35 / 0.87.
-    int threads = 64 * (NT <= 8 ? (nt_used + 1) / 2 : (nt_used + 3) / 4);
-    {
-        static int wv = -1;
-        if (wv < 0) { const char* e = getenv("CLIPX_ATTN_WAVES"); wv = e ? atoi(e) : 0; }
-        if (wv > 0 && wv <= nt_used && wv <= 16) threads = 64 * wv;
-    }
+    // (a dense batch whose L does not fill its NT tiles -- L <= 16 (NT - 1) -- takes the guarded form as well)
+    const bool packed = cu_rows != nullptr || nt_used != NT;
     if (bwd) {
-        // four-image backward (every operand read once) where its LDS (4 x LP x 128 B) still leaves >= 2 blocks per CU: NT <= 8.
-        // CLIPX_ATTN_BWD4=0 selects the two-image kernel; CLIPX_ATTN_BWD4_WAVES overrides its wave count.
-        static int bwd4 = -1, bwd4_waves = 0;
-        if (bwd4 < 0) {
-            const char* e = getenv("CLIPX_ATTN_BWD4");
-            bwd4 = (e && e[0] == '0') ? 0 : 1;
-            const char* w = getenv("CLIPX_ATTN_BWD4_WAVES");
-            bwd4_waves = w ? atoi(w) : 0;
-        }
-        if constexpr (NT <= 8) {
-            if (bwd4) {
-                const size_t lds4 = (size_t)4 * LP * AT_ROWB + 2 * LP * sizeof(float);
-                // one 16-row tile per wave up to 4 tiles (32.5 KiB of LDS: four blocks of four waves per CU); beyond that two
-                // tiles per wave -- measured at b = 4096 (scripts/bench_attn.py, profiles/r03_attention_bwd4.txt): L = 50: 4 waves
-                // 497 us, 3: 550, 2: 556 (two-image kernel 588); L = 77: 5 waves 937 us, 3: 572, 2: 687 (two-image 658)
-                int waves = NT <= 4 ? nt_used : (nt_used + 1) / 2;
-                if (bwd4_waves > 0 && bwd4_waves <= nt_used) waves = bwd4_waves;
-#define AT_BWD4(CAUSALV, PACKEDV)                                                                                                   \
-    do {                                                                                                                            \
-        (void)hipFuncSetAttribute((const void*)attn_bf16_bwd4_kernel<NT, CAUSALV, PACKEDV>,                                         \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);                                           \
-        hipLaunchKernelGGL((attn_bf16_bwd4_kernel<NT, CAUSALV, PACKEDV>), dim3(batch * heads), dim3(64 * waves), lds4, stream, L,   \
-                           heads, (const bf16_t*)qkv, (const bf16_t*)dout, (bf16_t*)out, seq_ids, cu_rows);                         \
-    } while (0)
-                // (a dense batch whose L does not fill its NT tiles -- L <= 16 (NT - 1) -- takes the guarded form as well)
-                const bool packed = cu_rows != nullptr || nt_used != NT;
-                if (causal) { if (packed) AT_BWD4(true, true); else AT_BWD4(true, false); }
-                else { if (packed) AT_BWD4(false, true); else AT_BWD4(false, false); }
-#undef AT_BWD4
-                CLIPX_LAUNCH_CHECK();
-                return 0;
-            }
-        }
-        (void)hipFuncSetAttribute((const void*)attn_bf16_bwd_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(attn_bf16_bwd_kernel<NT>, dim3(batch * heads), dim3(threads), lds, stream, L, heads, causal,
-                           (const bf16_t*)qkv, (const bf16_t*)dout, (bf16_t*)out, seq_ids, cu_rows);
+        // four images: 4 x LP x 128 B still leaves >= 2 blocks per CU at NT = 8
+        const size_t lds = (size_t)4 * LP * AT_ROWB + 2 * LP * sizeof(float);
+        // one 16-row tile per wave up to 4 tiles (32.5 KiB of LDS: four blocks of four waves per CU); beyond that two tiles per
+        // wave -- measured at b = 4096 (scripts/bench_attn.py, profiles/r03_attention_bwd4.txt): L = 50: 4 waves 497 us, 3: 550,
+        // 2: 556 (the earlier two-image kernel 588); L = 77: 5 waves 937 us, 3: 572, 2: 687 (two-image 658)
+        int waves = NT <= 4 ? nt_used : (nt_used + 1) / 2;
+        const int wv = attn_bwd4_waves_override();
+        if (wv > 0 && wv <= nt_used) waves = wv;
+        with_bools([&](auto causal_c, auto packed_c) {
+            auto kernel = attn_bf16_bwd4_kernel<NT, decltype(causal_c)::value, decltype(packed_c)::value>;
+            (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(kernel, dim3(batch * heads), dim3(64 * waves), lds, stream, L, heads, (const bf16_t*)qkv,
+                               (const bf16_t*)dout, (bf16_t*)out, seq_ids, cu_rows);
+        }, causal != 0, packed);
     } else {
-#define AT_FWD(CAUSALV, PACKEDV)                                                                                                    \
-    do {                                                                                                                            \
-        (void)hipFuncSetAttribute((const void*)attn_bf16_fwd_kernel<NT, CAUSALV, PACKEDV>,                                          \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                            \
-        hipLaunchKernelGGL((attn_bf16_fwd_kernel<NT, CAUSALV, PACKEDV>), dim3(batch * heads), dim3(threads), lds, stream, L, heads, \
-                           (const bf16_t*)qkv, (bf16_t*)out, seq_ids, cu_rows);                                                     \
-    } while (0)
-        const bool packed = cu_rows != nullptr || nt_used != NT;
-        if (causal) { if (packed) AT_FWD(true, true); else AT_FWD(true, false); }
-        else { if (packed) AT_FWD(false, true); else AT_FWD(false, false); }
-#undef AT_FWD
+        const size_t lds = (size_t)2 * LP * AT_ROWB;
+        // Two 16-row tiles per wave: blocks of half as many waves, so more (sample, head) blocks are resident per CU and one
+        // block's staging overlaps another's MFMA phase.  Measured at b=4096 (scripts/bench_attn.py): L=77 forward 412 -> 325 us
+        // (the two-image backward of the time 966 -> 728 us) with 3 waves instead of 5; one wave per block is slower again.
+        int waves = (nt_used + 1) / 2;
+        const int wv = attn_waves_override();
+        if (wv > 0 && wv <= nt_used && wv <= 16) waves = wv;
+        with_bools([&](auto causal_c, auto packed_c) {
+            auto kernel = attn_bf16_fwd_kernel<NT, decltype(causal_c)::value, decltype(packed_c)::value>;
+            (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(kernel, dim3(batch * heads), dim3(64 * waves), lds, stream, L, heads, (const bf16_t*)qkv,
+                               (bf16_t*)out, seq_ids, cu_rows);
+        }, causal != 0, packed);
     }
     CLIPX_LAUNCH_CHECK();
     return 0;
@@ -1791,33 +1494,27 @@ static int dispatch_gen(bool bwd, int batch, int L, int heads, int hd, int causa
     return -1;
 }
 
-// the shapes the online-softmax kernels take: the only ones with a log-sum-exp hand-over between forward and backward
+// =============================================================================== dispatch and C ABI
+// the shapes the online-softmax kernels take: the only ones with a log-sum-exp hand-over between forward and backward.
+// Head dim 64: the whole-sequence kernels up to 128 rows, these beyond.  (Until round 3 they started at 225 and a 14-tile
+// whole-sequence instantiation took 129..224: at L = 197 (ViT-B/16, b = 512 x 12 heads) it ran 0.249 / 0.667 ms fwd / bwd against
+// 0.194 / 0.580 ms for these kernels with two 8-wave blocks per CU and the log-sum-exp hand-over.)
 static bool bf16_long_applies(int L, int hd) {
-    static int force_generic = -1;
-    if (force_generic < 0) { const char* e = getenv("CLIPX_ATTN_GENERIC"); force_generic = (e && e[0] == '1') ? 1 : 0; }
-    // head dim 64: the whole-sequence kernels up to 128 rows, the online-softmax kernels beyond.  (Until round 3 they started at 225
-    // and a 14-tile whole-sequence instantiation took 129..224: at L = 197 (ViT-B/16, b = 512 x 12 heads) it ran 0.249 / 0.667 ms
-    // fwd / bwd against 0.194 / 0.580 ms for these kernels with two 8-wave blocks per CU and the log-sum-exp hand-over.)
-    static int long_from = -1;                                           // experiment: CLIPX_ATTN_LONG_FROM=<L>
-    if (long_from < 0) { const char* e = getenv("CLIPX_ATTN_LONG_FROM"); long_from = e ? atoi(e) : 129; }
-    if (force_generic) return false;
-    return (hd == 64 && L >= long_from && L <= atl_max_l<64>()) || (hd == 80 && L <= atl_max_l<80>());
+    if (attn_force_generic()) return false;
+    return (hd == 64 && L > 128 && L <= atl_max_l<64>()) || (hd == 80 && L <= atl_max_l<80>());
 }
 static int dispatch_bf16(bool bwd, int batch, int L, int heads, int hd, int causal, const void* qkv, const void* dout,
                          void* out, hipStream_t stream) {
-    static int force_generic = -1;
-    if (force_generic < 0) { const char* e = getenv("CLIPX_ATTN_GENERIC"); force_generic = (e && e[0] == '1') ? 1 : 0; }
     if (bf16_long_applies(L, hd)) {                                      // online-softmax MFMA kernels
         if (hd == 64) return launch_bf16_long<64>(bwd, batch, L, heads, causal, qkv, dout, out, stream);   // ViT-B/16, ViT-L/14-336
         return launch_bf16_long<80>(bwd, batch, L, heads, causal, qkv, dout, out, stream);                 // ViT-H/14
     }
-    if (hd != AT_HD || L > 224 || force_generic)       // MFMA kernels: head dim 64, whole sequence in LDS
+    if (hd != AT_HD || L > 128 || attn_force_generic())                  // whole-sequence MFMA kernels: head dim 64, L <= 128
         return dispatch_gen<bf16_t>(bwd, batch, L, heads, hd, causal, qkv, dout, out, stream);
     if (L <= 32) return launch_bf16<2>(bwd, batch, L, heads, causal, qkv, dout, out, stream);
     if (L <= 64) return launch_bf16<4>(bwd, batch, L, heads, causal, qkv, dout, out, stream);
     if (L <= 96) return launch_bf16<6>(bwd, batch, L, heads, causal, qkv, dout, out, stream);
-    if (L <= 128) return launch_bf16<8>(bwd, batch, L, heads, causal, qkv, dout, out, stream);
-    return launch_bf16<14>(bwd, batch, L, heads, causal, qkv, dout, out, stream);
+    return launch_bf16<8>(bwd, batch, L, heads, causal, qkv, dout, out, stream);
 }
 
 template <int HD>
@@ -1843,13 +1540,9 @@ static int dispatch(bool bwd, int dtype, int batch, int L, int heads, int hd, in
     if (batch <= 0) return 0;
     if (dtype == CLIPX_BF16) return dispatch_bf16(bwd, batch, L, heads, hd, causal, qkv, dout, out, stream);
     CLIPX_CHECK(dtype == CLIPX_F32, "attention: bad dtype");
-    {
-        static int force_generic = -1;
-        if (force_generic < 0) { const char* e = getenv("CLIPX_ATTN_GENERIC"); force_generic = (e && e[0] == '1') ? 1 : 0; }
-        const size_t whole = ((size_t)2 * L * hd + (bwd ? 2 * L : 0)) * sizeof(float);
-        if (whole > 160 * 1024 || force_generic || (hd != 32 && hd != 64 && hd != 80))
-            return dispatch_gen<float>(bwd, batch, L, heads, hd, causal, qkv, dout, out, stream);
-    }
+    const size_t whole = ((size_t)2 * L * hd + (bwd ? 2 * L : 0)) * sizeof(float);
+    if (whole > 160 * 1024 || attn_force_generic() || (hd != 32 && hd != 64 && hd != 80))
+        return dispatch_gen<float>(bwd, batch, L, heads, hd, causal, qkv, dout, out, stream);
     if (hd == 32) return launch_f32<32>(bwd, batch, L, heads, causal, qkv, dout, out, stream);
     if (hd == 64) return launch_f32<64>(bwd, batch, L, heads, causal, qkv, dout, out, stream);
     if (hd == 80) return launch_f32<80>(bwd, batch, L, heads, causal, qkv, dout, out, stream);

@@ -27,7 +27,7 @@ python scripts/kstats.py $F/prof512 27 0.05 > $F/kstats_b512.txt
 bash scripts/collect_pmc.sh > $F/pmc.log 2>&1; head -12 gpurun_out/pmc_${ROUND}_traffic_entry.json
 python scripts/bench_gemm.py > $F/gemm_vs_hipblaslt.txt 2>&1; tail -4 $F/gemm_vs_hipblaslt.txt
 python scripts/bench_epi.py > $F/epilogue_variants.txt 2>&1
-python scripts/bench_attn.py > $F/attention.txt 2>&1; CLIPX_ATTN_BWD4=0 python scripts/bench_attn.py > $F/attention_two_image_bwd.txt 2>&1; tail -2 $F/attention.txt
+python scripts/bench_attn.py > $F/attention.txt 2>&1; tail -2 $F/attention.txt
 python scripts/bench_colclip.py 256 512 > $F/colclip.txt 2>&1; tail -4 $F/colclip.txt
 for S in h14 long b16; do python scripts/bench_attn.py 256 $S > $F/attention_$S.txt 2>&1; done; mv $F/attention_long.txt $F/attention_l14.txt
 python bench.py --model ViT-B-16 --global-batch 512 --steps 10 --warmup 3 --full --no-cpu-baseline --no-dense-compare > $F/bench_b16_b512.json 2> $F/bench_b16.err; echo "b16 rc=$?"

@@ -6,6 +6,12 @@ Compiles with the line tests/test_isa_guards.py uses and prints, per kernel symb
 static LDS, instructions, and the counts of v_mfma, ds_read_b128, LDS-DMA loads, s_barrier, s_waitcnt with vmcnt(0), v_writelane.
 `kloop` lists, per k-step body in the text (from the first fragment read of a burst to the last MFMA that follows it), how many
 v_writelane / v_readlane / scratch_* / vmcnt(0) instructions sit inside it: all zeros = nothing spilled or drained in the loop.
+
+    python scripts/isa_table.py colxlip_amd/csrc/attention.hip --identical-to colxlip_amd/csrc/attention_parent.hip
+
+compares a refactored source with an earlier revision of it (saved beside it, so that its includes resolve): per kernel symbol
+VGPRs, scratch, occupancy, instructions and whether the instruction stream is the other revision's (comments and directives
+dropped, .LBB labels numbered by first appearance), then the symbols that only the other revision has.
 """
 import argparse
 import os
@@ -75,10 +81,36 @@ def table(src, prefix):
         print(" ".join("%8s" % (v,) for v in r))
 
 
+def stream(body):
+    lines = [l.split(";")[0].strip() for l in body.split("\n")]
+    text = "\n".join(l for l in lines if l and not l.startswith("//") and (not l.startswith(".") or l.endswith(":")))
+    labels = {}
+    return re.sub(r"\.LBB\d+_\d+", lambda m: labels.setdefault(m.group(0), ".L%d" % len(labels)), text)
+
+
+def identity(src, other, prefix):
+    def load(path):
+        asm, remarks = compile_asm(path)
+        res = {m.group(1): tuple(int(re.search(re.escape(k) + r": (\d+)", m.group(2)).group(1))
+                                 for k in ("VGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]"))
+               for m in re.finditer(r"Function Name: (\S+)(.*?)(?=Function Name:|\Z)", remarks, re.S)}
+        return res, {m.group(1): stream(m.group(2)) for m in re.finditer(r"^(%s\w*):[^\n]*\n(.*?)^\.Lfunc_end" % prefix, asm, re.S | re.M)}
+    res, new = load(src)
+    old_res, old = load(other)
+    same = sum(1 for n in new if old.get(n) == new[n])
+    print("# %s against %s: %d kernels, %d with the other revision's instruction stream" % (os.path.basename(src), os.path.basename(other), len(new), same))
+    print("%-84s %5s %5s %4s %6s %s" % ("kernel", "vgpr", "scr", "occ", "instr", "identical"))
+    for n in sorted(new):
+        print("%-84s %5d %5d %4d %6d %s" % ((n,) + res[n] + (len(instructions(new[n])), "yes" if old.get(n) == new[n] else "NO")))
+    for n in sorted(set(old) - set(new)):
+        print("only in %s: %-60s vgpr %d scr %d occ %d" % ((os.path.basename(other), n) + old_res[n]))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("sources", nargs="+")
     ap.add_argument("--prefix", default="_Z", help="kernel symbol prefix")
+    ap.add_argument("--identical-to", help="an earlier revision of the (one) source: compare instruction streams instead")
     a = ap.parse_args()
     for s in a.sources:
-        table(s, a.prefix)
+        identity(s, a.identical_to, a.prefix) if a.identical_to else table(s, a.prefix)

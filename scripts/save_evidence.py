@@ -57,10 +57,9 @@ for s, d in cp.items():
     else:
         print("missing", s)
 with open(f"profiles/{R}_attention_bwd4.txt", "w") as f:
-    f.write("scripts/bench_attn.py (b = 4096): four-image backward (default) then CLIPX_ATTN_BWD4=0 (two-image backward)\n")
-    for name in ("attention.txt", "attention_two_image_bwd.txt"):
-        if os.path.exists(f"{F}/{name}"):
-            f.write(f"== {name}\n" + "".join(l for l in open(f"{F}/{name}") if "TB/s" in l))
+    f.write("scripts/bench_attn.py (b = 4096): four-image backward\n")
+    if os.path.exists(f"{F}/attention.txt"):
+        f.write("".join(l for l in open(f"{F}/attention.txt") if "TB/s" in l))
 with open(f"profiles/{R}_attention_other_models.txt", "w") as f:
     f.write("scripts/bench_attn.py 256 {h14,long,b16}: the online-softmax kernels at the other BASELINE models' shapes (end of the round)\n")
     for name in ("attention_h14.txt", "attention_l14.txt", "attention_b16.txt"):
