@@ -271,6 +271,61 @@ __global__ __launch_bounds__(256) void maxsim_mean_kernel(int nt, int ni, int ld
     }
 }
 
+// Forward-only scoring (retrieval, ColXLIP.get_logits under no_grad): slot partials -> final scores in one pass, with neither
+// maxvT / argT nor inv_count in memory.  For text samples m < nm (packed rows cu[m] .. cu[m+1], chunk-local row = r - rbase) and
+// images k < ni of the partial arrays' image chunk:
+//     tok[m, k]    = sum_r w_r v_r / (sum_r w_r [v_r != 0] + 1e-8),  v_r = max over the slot segments of image k (as finish)
+//     scores[k, m] = scale * (alpha * G[k, m] + beta * tok[m, k]),  beta = 1 - alpha   (image-major; G == nullptr: no global term)
+// The partials are row-contiguous and a sample's rows are consecutive, so a wave owns one image and walks SPW consecutive
+// samples with its lanes on consecutive rows (256-byte reads per segment; > 64 rows take another pass) and reduces (sum,
+// count) across the wave; lane i keeps sample i's score, and the SPW scores leave as one 64-byte store.  pmax == nullptr is
+// the global-only form (alpha = 1): scale * G bit for bit, the token term is skipped, not multiplied by 0.
+#define MAXSIM_FOLD_SPW 16
+__global__ __launch_bounds__(256) void maxsim_score_fold_kernel(int nm, int ni, int q, int ldp, int rbase, const int* __restrict__ cu,
+                                                                const float* __restrict__ row_w, const float* __restrict__ pmax,
+                                                                const float* __restrict__ G, long ld_g, float* __restrict__ scores,
+                                                                long ld_scores, float alpha, float beta, float scale) {
+    const int lane = threadIdx.x & 63;
+    const int k = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (k >= ni) return;
+    const int mb = blockIdx.x * MAXSIM_FOLD_SPW;
+    const int mcnt = min(MAXSIM_FOLD_SPW, nm - mb);
+    float tok = 0.f;
+    if (pmax) {
+        const int s_lo = (k * q) >> 6, s_hi = ((k + 1) * q - 1) >> 6;
+        for (int i = 0; i < mcnt; ++i) {
+            const int ra = cu[mb + i] - rbase, rb = cu[mb + i + 1] - rbase;
+            float s = 0.f, c = 0.f;
+            for (int r = ra + lane; r < rb; r += 64) {
+                float best = -INFINITY;
+                for (int sl = s_lo; sl <= s_hi; ++sl) {
+                    const int seg = ((sl << 6) / q == k) ? 0 : 1;
+                    const float v = pmax[(long)(2 * sl + seg) * ldp + r];
+                    best = v > best ? v : best;
+                }
+                const float w = row_w[rbase + r];
+                s += w * best;
+                c += (best != 0.f) ? w : 0.f;
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                s += __shfl_xor(s, o, 64);
+                c += __shfl_xor(c, o, 64);
+            }
+            if (lane == i) tok = s / (c + 1e-8f);
+        }
+    }
+    if (lane < mcnt) {
+        const int m = mb + lane;
+        float out;
+        // every product and the sum rounded on its own (no fma contraction): the same fp32 values as the expression written out
+        if (!pmax) out = __fmul_rn(scale, G[(long)k * ld_g + m]);
+        else if (G) out = __fmul_rn(scale, __fadd_rn(__fmul_rn(alpha, G[(long)k * ld_g + m]), __fmul_rn(beta, tok)));
+        else out = __fmul_rn(scale, __fmul_rn(beta, tok));
+        scores[(long)k * ld_scores + m] = out;
+    }
+}
+
 // d(S) on the packed rows: P[r, k*q + qq] = (qq == argT[k, r]) ? dlogits[m_r, k] * inv_count[m_r, k] : 0   (bf16).
 // One block per packed row; 8 columns (16 B) per thread and pass.
 __global__ __launch_bounds__(256) void maxsim_scatter_packed_kernel(int r0, int ld, int ni, int q, const int* __restrict__ row_m,
@@ -355,6 +410,19 @@ extern "C" int clipx_maxsim_finish(int R, int ldp, int r0, int ld, int ni, int q
     if (R <= 0 || ni <= 0) return 0;
     hipLaunchKernelGGL(maxsim_finish_kernel, dim3(cdiv(R, 256), ni), dim3(256), 0, (hipStream_t)stream, R, ldp, r0, ld, ni, q, pmax,
                        pidx, maxvT, argT);
+    CLIPX_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int clipx_maxsim_score_fold(int nm, int ni, int q, int ldp, int rbase, const int* cu, const float* row_w, const float* pmax,
+                                       const float* G, long ld_g, float* scores, long ld_scores, float alpha, float beta, float scale,
+                                       void* stream) {
+    CLIPX_CHECK(pmax || G, "maxsim_score_fold: the global-only form (no partials) needs G");
+    CLIPX_CHECK(!pmax || (q >= 64 && ldp >= 1 && cu && row_w), "maxsim_score_fold: partials need q >= 64, cu and row_w (q=%d)", q);
+    CLIPX_CHECK(ni <= 4 * 65535, "maxsim_score_fold: at most 262140 images per call (got %d)", ni);
+    if (nm <= 0 || ni <= 0) return 0;
+    hipLaunchKernelGGL(maxsim_score_fold_kernel, dim3(cdiv(nm, MAXSIM_FOLD_SPW), cdiv(ni, 4)), dim3(256), 0, (hipStream_t)stream, nm, ni,
+                       q, ldp, rbase, cu, row_w, pmax, G, ld_g, scores, ld_scores, alpha, beta, scale);
     CLIPX_LAUNCH_CHECK();
     return 0;
 }

@@ -1589,6 +1589,29 @@ class ColXLIP(CLIP):
             tokens = l2_normalize(tokens.float()).to(tokens.dtype)
         return feat, tokens.view(batch, L, -1)
 
+    def get_logits(self, image, text, alpha: Optional[float] = None):
+        """(logits_per_image [B_i, B_t], logits_per_text): logit_scale.exp() * (alpha * I T^T + (1 - alpha) * MaxSim(tokens)^T),
+        the scoring the reference's forward carries as a commented-out block (model.py:670-685); `alpha` defaults to self.alpha.
+        With grad enabled it is composed of the differentiable pieces the loss uses; under no_grad it is `ops.maxsim_scores`."""
+        alpha = self.alpha if alpha is None else float(alpha)
+        image_features, token_image_features = self.encode_image(image, normalize=True)
+        text_features, token_text_features = self.encode_text(text, normalize=True)
+        if not torch.is_grad_enabled():
+            from .train import similarity_matrix
+            image_logits = ops.maxsim_scores(token_image_features, token_text_features,
+                                             similarity_matrix(image_features, text_features), alpha,
+                                             float(self.logit_scale.exp()))
+        else:
+            from .loss import _ScaledMatmul, compute_colbert_similarity
+            scale = self.logit_scale.exp()
+            image_logits = _ScaledMatmul.apply(image_features, text_features, scale)
+            if alpha != 1.0:
+                token_logits = scale * compute_colbert_similarity(token_image_features, token_text_features).T
+                image_logits = alpha * image_logits + (1 - alpha) * token_logits
+        if self.logit_bias is not None:
+            image_logits = image_logits + self.logit_bias
+        return image_logits, image_logits.T
+
     def forward(self, image: Optional[torch.Tensor] = None, text: Optional[torch.Tensor] = None, alpha: Optional[float] = None):
         if image is None and text is None:
             return {}

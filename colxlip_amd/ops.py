@@ -898,3 +898,162 @@ def retrieval_rank(scores, tgt_off, tgt_idx):
     check(_lib.lib().clipx_retrieval_rank(rows, cols, _p(scores), scores.stride(0), _p(tgt_off), _p(tgt_idx), _p(ranks),
                                           _stream()))
     return ranks
+
+
+# ------------------------------------------------------------------ late-interaction scoring (forward only)
+MAXSIM_OPERAND_BYTES = (1 << 31) - 1     # one image chunk of the MaxSim GEMM stays addressable through a 2-GiB buffer descriptor
+MAXSIM_MAX_IMAGES = 65535                # images per chunk
+MAXSIM_TARGET_ROWS = 4096                # an image chunk is shrunk until a text chunk of this many packed rows fits the partials
+
+
+def maxsim_partial_ld(rows: int) -> int:
+    """leading dimension of the partial arrays of a text chunk: its packed rows, rounded up to 64 bytes of fp32"""
+    return (rows + 15) // 16 * 16
+
+
+def maxsim_partial_bytes(ci: int, q: int, rows: int) -> int:
+    """pmax (fp32) + pidx (int16) of `ci` images against `rows` packed rows: 6 bytes per (row, 64-column slot, segment)"""
+    return 12 * ((ci * q + 63) // 64) * maxsim_partial_ld(rows)
+
+
+def plan_maxsim_chunks(ni, q, e, cu_host, partial_bytes, operand_bytes=None):
+    """Chunk plan of `maxsim_scores` on the fused route; pure Python.  Returns (image_chunks, text_chunks):
+      image_chunks [(k0, k1, ci)]: images k0 .. k1 go through the GEMM as `ci >= k1 - k0` images, the last ci - (k1 - k0) of
+        them zero padding, with (ci * q) % 8 == 0 (GEMM alignment), ci <= 65535 and ci * q * e bf16 elements below
+        `operand_bytes`; only the last chunk can need padding;
+      text_chunks [(m0, m1, r0, r1)]: runs of whole samples (packed rows cu[m0] = r0 .. cu[m1] = r1) whose partial arrays
+        against the largest image chunk stay within `partial_bytes`; a single sample that does not fit is a chunk of its own.
+    The image chunk is as large as the operand limit allows, but no larger than lets MAXSIM_TARGET_ROWS packed rows (or all of
+    them) fit the partials: the GEMM wants a tall operand more than a wide one."""
+    import math
+    if operand_bytes is None:
+        operand_bytes = MAXSIM_OPERAND_BYTES
+    nt = len(cu_host) - 1
+    unit = 8 // math.gcd(q, 8)                                   # image counts with (ci * q) % 8 == 0
+    want_ld = maxsim_partial_ld(max(1, min(MAXSIM_TARGET_ROWS, cu_host[nt])))
+    cmax = min(MAXSIM_MAX_IMAGES, operand_bytes // (2 * q * e), (partial_bytes // (12 * want_ld)) * 64 // q)
+    cmax = max(unit, cmax // unit * unit)
+    cmax = min(cmax, (ni + unit - 1) // unit * unit)
+    image_chunks = []
+    for k0 in range(0, ni, cmax):
+        k1 = min(ni, k0 + cmax)
+        image_chunks.append((k0, k1, (k1 - k0 + unit - 1) // unit * unit))
+    slots = (cmax * q + 63) // 64
+    limit_rows = partial_bytes // (12 * slots) // 16 * 16
+    text_chunks, m0 = [], 0
+    while m0 < nt:
+        m1 = m0 + 1
+        while m1 < nt and cu_host[m1 + 1] - cu_host[m0] <= limit_rows:
+            m1 += 1
+        text_chunks.append((m0, m1, cu_host[m0], cu_host[m1]))
+        m0 = m1
+    return image_chunks, text_chunks
+
+
+def maxsim_score_fold(nm, ni, q, ldp, rbase, cu, m0, row_w, pmax, G, scores, alpha, scale):
+    """Partials of one (image chunk, text chunk) -> scores[:ni, :nm] = scale * (alpha * G[:ni, :nm] + (1 - alpha) * tok^T);
+    `G` and `scores` are views of the block (unit column stride).  pmax None: scale * G exactly."""
+    assert scores.dtype == torch.float32 and scores.stride(1) == 1 and scores.shape[0] >= ni and scores.shape[1] >= nm
+    if G is not None:
+        assert G.dtype == torch.float32 and G.stride(1) == 1 and G.shape[0] >= ni and G.shape[1] >= nm
+    cu_ptr = None if cu is None else cu.data_ptr() + 4 * m0
+    check(_lib.lib().clipx_maxsim_score_fold(nm, ni, q, ldp, rbase, cu_ptr, _p(row_w), _p(pmax), _p(G),
+                                             0 if G is None else G.stride(0), _p(scores), scores.stride(0), float(alpha),
+                                             float(1.0 - alpha), float(scale), _stream()))
+    return scores
+
+
+def maxsim_fused_applies(tok_img, tok_txt) -> bool:
+    """the shapes `_MaxSimFused.applies` takes, without its image-count alignment (the chunk plan pads the last chunk)"""
+    ni, q, e = tok_img.shape
+    return (tok_txt.dtype == torch.bfloat16 and tok_img.dtype == torch.bfloat16 and tok_txt.is_cuda and 64 <= q <= 65535
+            and e % 64 == 0 and e >= 128 and os.environ.get("CLIPX_MAXSIM_FUSED", "1") != "0")
+
+
+def _maxsim_scores_fused(tok_img, tok_txt, G, alpha, scale, out):
+    from .loss import _MaxSimFused
+    ni, q, e = tok_img.shape
+    dev = tok_img.device
+    img = tok_img.contiguous().view(ni * q, e)
+    txt = tok_txt.contiguous()
+    cu, R = maxsim_pack_text(txt)
+    packed, _, row_w = maxsim_pack_rows(txt, cu, R)
+    image_chunks, text_chunks = plan_maxsim_chunks(ni, q, e, cu.cpu().tolist(), _MaxSimFused.CHUNK_BYTES)
+    cmax = max(c for _, _, c in image_chunks)
+    ldmax = maxsim_partial_ld(max(r1 - r0 for _, _, r0, r1 in text_chunks))
+    slots = (cmax * q + 63) // 64
+    pmax = torch.empty((2 * slots * ldmax,), dtype=torch.float32, device=dev)
+    pidx = torch.empty((2 * slots * ldmax,), dtype=torch.int16, device=dev)
+    for k0, k1, ci in image_chunks:
+        if ci == k1 - k0:
+            op = img[k0 * q:k1 * q]
+        else:                                                   # zero images behind the last ones: their columns are never folded
+            op = torch.zeros((ci * q, e), dtype=img.dtype, device=dev)
+            op[:(k1 - k0) * q] = img[k0 * q:k1 * q]
+        for m0, m1, r0, r1 in text_chunks:
+            ldp = maxsim_partial_ld(r1 - r0)
+            maxsim_gemm(packed[r0:r1], op, ci, q, pmax, pidx, ldp)
+            maxsim_score_fold(m1 - m0, k1 - k0, q, ldp, r0, cu, m0, row_w, pmax, None if G is None else G[k0:k1, m0:m1],
+                              out[k0:k1, m0:m1], alpha, scale)
+    return out
+
+
+def _maxsim_scores_general(tok_img, tok_txt, G, alpha, scale, out):
+    from .loss import _MaxSimLogits
+    ni, q, e = tok_img.shape
+    nt, n, _ = tok_txt.shape
+    img = tok_img.contiguous().float().view(ni * q, e)
+    txt = tok_txt.contiguous().float().view(nt * n, e)
+    limit = _MaxSimLogits.CHUNK_BYTES
+    ci = max(1, min(ni, limit // max(1, 4 * n * q)))           # images per chunk: one sample's similarities fit
+    ct = max(1, min(nt, limit // max(1, 4 * n * ci * q)))
+    for k0 in range(0, ni, ci):
+        k1 = min(ni, k0 + ci)
+        cols = (k1 - k0) * q
+        for m0 in range(0, nt, ct):
+            m1 = min(nt, m0 + ct)
+            rows = (m1 - m0) * n
+            S = torch.empty((rows, cols), dtype=torch.float32, device=img.device)
+            gemm_f32(rows, cols, e, txt[m0 * n:m1 * n], e, 1, img[k0 * q:k1 * q], 1, e, S, cols)
+            maxv, _ = maxsim_reduce(S, q)
+            del S
+            tok, _ = masked_mean(maxv, m1 - m0, n)              # [m, k]
+            blk = (1.0 - alpha) * tok.t()
+            if G is not None:
+                blk = alpha * G[k0:k1, m0:m1] + blk
+            out[k0:k1, m0:m1] = scale * blk
+    return out
+
+
+def maxsim_scores(tok_img, tok_txt, G, alpha, scale, out=None):
+    """Late-interaction scores without autograd: scores [ni, nt] (fp32, image-major) =
+        scale * (alpha * G + (1 - alpha) * MaxSim(tok_img [ni, q, e], tok_txt [nt, n, e])^T)
+    with MaxSim the reference's compute_colbert_similarity (loss.py:20-46) and G [ni, nt] the fp32 global similarities (None:
+    no global term).  bf16 tokens with q >= 64 and e % 64 == 0 go through the MaxSim GEMM and `clipx_maxsim_score_fold` per
+    (image chunk x text chunk): nothing of size rows x images is kept.  Everything else (fp32 tokens, q < 64, other embed dims)
+    runs in fp32 on gemm_f32 + maxsim_reduce + masked_mean.  alpha = 1 is scale * G bit for bit: no token kernel runs and the
+    token features are not looked at (they may be None)."""
+    alpha, scale = float(alpha), float(scale)
+    if alpha == 1.0:
+        assert G is not None, "maxsim_scores: alpha = 1 scores with the global similarities only and needs G"
+        ni, nt = G.shape
+    else:
+        ni, q, e = tok_img.shape
+        nt, n, e2 = tok_txt.shape
+        assert e == e2 and tok_img.dtype == tok_txt.dtype and tok_img.is_cuda
+    if G is not None:
+        assert G.shape == (ni, nt) and G.dtype == torch.float32
+        if G.stride(1) != 1:
+            G = G.contiguous()
+    if out is None:
+        out = torch.empty((ni, nt), dtype=torch.float32, device=G.device if G is not None else tok_img.device)
+    assert out.shape == (ni, nt) and out.dtype == torch.float32 and out.stride(1) == 1
+    with torch.no_grad():
+        if alpha == 1.0:
+            for k0 in range(0, ni, 4 * MAXSIM_MAX_IMAGES):
+                k1 = min(ni, k0 + 4 * MAXSIM_MAX_IMAGES)
+                maxsim_score_fold(nt, k1 - k0, 0, 0, 0, None, 0, None, None, G[k0:k1], out[k0:k1], 1.0, scale)
+            return out
+        if maxsim_fused_applies(tok_img, tok_txt):
+            return _maxsim_scores_fused(tok_img.detach(), tok_txt.detach(), G, alpha, scale, out)
+        return _maxsim_scores_general(tok_img.detach(), tok_txt.detach(), G, alpha, scale, out)

@@ -118,6 +118,8 @@ _FLAGS = {
     "--distill-model": dict(default=None),
     "--distill-pretrained": dict(default=None),
     "--inference-with-flair": _flag(),
+    # a ColXLIP model is scored on its global features only (the reference's `original_clip` mode; the same as --alpha 1)
+    "--evaluate-as-original-clip": _flag(),
     # ---- loss
     "--local-loss": _flag(),
     "--gather-with-grad": _flag(),

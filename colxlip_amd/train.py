@@ -267,24 +267,60 @@ def evaluate(model, data, epoch, args, tb_writer=None, tokenizer=None):
     return metrics
 
 
-def encode_split(model, txt_loader, img_loader, device, input_dtype=None):
+def encode_split(model, txt_loader, img_loader, device, input_dtype=None, with_tokens=False):
     """(image_features [n_img, E], image ids, text_features [n_txt, E], caption ids): every batch of the two loaders through
     `encode_text` / `encode_image(normalize=True)` without a graph; features stay on the device (the reference moves every
-    batch to the CPU and encodes images one at a time, train.py:520-541,590-606)."""
+    batch to the CPU and encodes images one at a time, train.py:520-541,590-606).  A model whose encoders return (pooled,
+    tokens) pairs (ColXLIP) contributes its pooled features here; with `with_tokens` the normalised token features, on the
+    device in the model's compute dtype, follow as a fifth and sixth value ([n_img, q, E], [n_txt, n, E])."""
     core = unwrap_model(model)
-    feats_t, ids_t, feats_i, ids_i = [], [], [], []
+    feats_t, ids_t, feats_i, ids_i, toks_t, toks_i = [], [], [], [], [], []
+
+    def keep(out, feats, toks):
+        if isinstance(out, tuple):
+            if with_tokens:
+                toks.append(out[1])
+            out = out[0]
+        feats.append(out.float())
+
     with torch.no_grad():
         for texts, cap_id in txt_loader:
             texts = texts.to(device=device, non_blocking=True)
             if texts.ndim == 3:
                 texts = texts[:, 0]
-            feats_t.append(core.encode_text(texts.contiguous(), normalize=True).float())
+            keep(core.encode_text(texts.contiguous(), normalize=True), feats_t, toks_t)
             ids_t.append(torch.as_tensor(cap_id).reshape(-1).cpu())
         for images, img_id in img_loader:
             images = images.to(device=device, dtype=input_dtype, non_blocking=True)
-            feats_i.append(core.encode_image(images, normalize=True).float())
+            keep(core.encode_image(images, normalize=True), feats_i, toks_i)
             ids_i.append(torch.as_tensor(img_id).reshape(-1).cpu())
-    return torch.cat(feats_i), torch.cat(ids_i), torch.cat(feats_t), torch.cat(ids_t)
+    found = (torch.cat(feats_i), torch.cat(ids_i), torch.cat(feats_t), torch.cat(ids_t))
+    if with_tokens:
+        if not toks_i or not toks_t:
+            raise ValueError("encode_split(with_tokens=True): the model's encoders return no token features")
+        found += (torch.cat(toks_i), torch.cat(toks_t))
+    return found
+
+
+def is_late_interaction(model) -> bool:
+    """a model that scores with alpha * global + (1 - alpha) * token MaxSim (ColXLIP)"""
+    from .model import ColXLIP
+    return isinstance(unwrap_model(model), ColXLIP)
+
+
+def late_interaction_scores(model, txt_loader, img_loader, device, input_dtype=None, alpha=0.5):
+    """(scores [n_img, n_txt] fp32, image ids, caption ids) of a ColXLIP model on one retrieval split:
+    logit_scale.exp() * (alpha * I T^T + (1 - alpha) * MaxSim(tokens)^T) -- the scoring the reference's ColXLIP.forward carries
+    as a commented-out block (model.py:670-685) -- on `ops.maxsim_scores`.  alpha = 1 is the reference's `original_clip` mode:
+    the token features are then not even collected."""
+    tokens = alpha != 1.0
+    found = encode_split(model, txt_loader, img_loader, device, input_dtype, with_tokens=tokens)
+    feats_i, img_ids, feats_t, cap_ids = found[:4]
+    with torch.no_grad():
+        scale = float(unwrap_model(model).logit_scale.exp())
+        G = similarity_matrix(feats_i, feats_t)
+        scores = ops.maxsim_scores(found[4], found[5], G, alpha, scale) if tokens else ops.maxsim_scores(None, None, G, 1.0, scale)
+    return scores, img_ids, cap_ids
 
 
 def remap_indices(img_ids, cap_ids, img2txt_dict, txt2img_dict):
@@ -300,12 +336,17 @@ def remap_indices(img_ids, cap_ids, img2txt_dict, txt2img_dict):
 
 def retrieval_on_split(keyword, model, txt_loader, img_loader, img2txt_dict, txt2img_dict, args, epoch, metrics, device,
                        input_dtype=None, autocast=None):
-    """reference train.py:510-587 (`original_clip` mode).  `autocast` is accepted for signature compatibility and unused:
-    precision lives inside the model."""
-    feats_i, img_ids, feats_t, cap_ids = encode_split(model, txt_loader, img_loader, device, input_dtype)
-    with torch.no_grad():
-        scale = unwrap_model(model).logit_scale.exp().float()
-        scores = similarity_matrix(feats_i * scale, feats_t)                  # [n_img, n_txt], as train.py:608
+    """reference train.py:510-587 (`original_clip` mode).  A ColXLIP model is scored by late interaction with `args.alpha`
+    (`late_interaction_scores`), or on its global features alone under --evaluate-as-original-clip; the ranking and the metric
+    names are the same.  `autocast` is accepted for signature compatibility and unused: precision lives inside the model."""
+    if is_late_interaction(model):
+        alpha = 1.0 if getattr(args, "evaluate_as_original_clip", False) else float(getattr(args, "alpha", 0.5))
+        scores, img_ids, cap_ids = late_interaction_scores(model, txt_loader, img_loader, device, input_dtype, alpha)
+    else:
+        feats_i, img_ids, feats_t, cap_ids = encode_split(model, txt_loader, img_loader, device, input_dtype)
+        with torch.no_grad():
+            scale = unwrap_model(model).logit_scale.exp().float()
+            scores = similarity_matrix(feats_i * scale, feats_t)              # [n_img, n_txt], as train.py:608
     img2txt, txt2img = remap_indices(img_ids, cap_ids, img2txt_dict, txt2img_dict)
     found = compute_retrieval(scores, txt2img, img2txt)
     prefix = keyword + "_" if keyword else ""

@@ -436,6 +436,14 @@ int clipx_maxsim_finish(int R, int ldp, int r0, int ld, int ni, int q, const flo
                         float* maxvT, unsigned short* argT, void* stream);
 int clipx_maxsim_mean(int nt, int ni, int ld, const int* cu, const float* row_w, const float* maxvT, float* logits,
                       float* inv_count, void* stream);
+/* score_fold (forward only: retrieval, get_logits without grad): the partials of one (image chunk, text chunk) straight to a
+ * block of the dense image-major score matrix, scores[k, m] = scale * (alpha * G[k, m] + beta * tok[m, k]) for samples m < nm
+ * (cu points at the chunk's first sample, packed rows cu[m] - rbase .. cu[m+1] - rbase of the partials, weights row_w[cu[m] ..])
+ * and images k < ni, tok = the masked mean of maxsim_mean over the per-row maxima of maxsim_finish; G, scores point at the
+ * block's first element.  G == NULL: no global term.  pmax == NULL: scale * G exactly (alpha = 1; the token term is skipped). */
+int clipx_maxsim_score_fold(int nm, int ni, int q, int ldp, int rbase, const int* cu, const float* row_w, const float* pmax,
+                            const float* G, long ld_g, float* scores, long ld_scores, float alpha, float beta, float scale,
+                            void* stream);
 int clipx_maxsim_scatter_packed(int R, int r0, int ld, int ni, int q, const int* row_m, const float* dlogits,
                                 const float* inv_count, const unsigned short* argT, void* P, void* stream);
 int clipx_maxsim_scale_rows(int R, int e, const float* row_w, const void* x, void* y, void* stream);
