@@ -390,6 +390,61 @@ def patchify(image, P, Kp, dtype):
     return out
 
 
+IMAGE_MAX_SCALE = 16        # box / virtual output per axis: IT_MAX_SCALE of csrc/image_transform.hip
+
+
+def image_geometry(offsets, hw, box, vsize, origin, out_hw, nbytes, allow_partial=False):
+    """Validate the per-image geometry of `image_transform` on the host and pack it into the kernel's records: a CPU int64
+    tensor [n, 6] (48 bytes per image: int64 offset, then int32 h, w, top, left, bh, bw, vh, vw, oy, ox).
+    offsets [n] byte offset of each HWC uint8 image in a buffer of `nbytes`; hw [n, 2] its (h, w); box [n, 4] source box
+    (top, left, bh, bw); vsize [n, 2] virtual output (vh, vw); origin [n, 2] origin (oy, ox) of the out_hw window in it.
+    Raises ValueError -- before anything is launched -- for an image outside the buffer, a box outside its image, a window outside
+    the virtual output, or a scale (box / virtual size) above IMAGE_MAX_SCALE on either axis.  allow_partial: a window may reach
+    past the right / bottom edge of its virtual output; the kernel leaves that part of the output untouched."""
+    H, W = int(out_hw[0]), int(out_hw[1])
+    offsets = torch.as_tensor(offsets, dtype=torch.int64).reshape(-1)
+    n = offsets.numel()
+    geom = torch.cat([torch.as_tensor(t, dtype=torch.int64).reshape(n, k) for t, k in ((hw, 2), (box, 4), (vsize, 2), (origin, 2))],
+                     dim=1)
+    h, w, top, left, bh, bw, vh, vw, oy, ox = geom.unbind(1)
+    if H < 1 or W < 1:
+        raise ValueError(f"image_transform: output size {H} x {W}")
+    if n and bool(((h < 1) | (w < 1) | (offsets < 0) | (offsets + 3 * h * w > int(nbytes))).any()):
+        raise ValueError("image_transform: an image does not lie inside the byte buffer")
+    if n and bool(((top < 0) | (left < 0) | (bh < 1) | (bw < 1) | (top + bh > h) | (left + bw > w)).any()):
+        raise ValueError("image_transform: a source box does not lie inside its image")
+    outside = ((oy >= vh) | (ox >= vw)) if allow_partial else ((oy + H > vh) | (ox + W > vw))
+    if n and bool(((vh < 1) | (vw < 1) | (oy < 0) | (ox < 0) | outside).any()):
+        raise ValueError("image_transform: the output window does not lie inside the virtual output")
+    if n and bool(((bh > IMAGE_MAX_SCALE * vh) | (bw > IMAGE_MAX_SCALE * vw)).any()):
+        raise ValueError(f"image_transform: a box is more than {IMAGE_MAX_SCALE}x its output size on an axis "
+                         "(store smaller images: python -m colxlip_amd.pack --max-side)")
+    meta = torch.empty((n, 6), dtype=torch.int64)
+    meta[:, 0] = offsets
+    meta.view(torch.int32)[:, 2:] = geom.to(torch.int32)
+    return meta
+
+
+@family("embed")
+def image_transform(data, meta, out_hw, mean, std, interpolation="bicubic", dtype=torch.float32, out=None):
+    """uint8 HWC images -> normalised [n, 3, H, W] `dtype` (fp32 | bf16): crop, PIL-exact two-pass resample (bicubic | bilinear),
+    (level / 255 - mean) / std, in one kernel.  data: 1-D uint8 device buffer; meta: the records of `image_geometry` (a CPU tensor
+    is copied to the device; a device tensor is used as it is and must come from `image_geometry`)."""
+    if interpolation not in ("bicubic", "bilinear"):
+        raise ValueError(f"image_transform: interpolation {interpolation!r} (bicubic | bilinear)")
+    assert data.dtype == torch.uint8 and data.dim() == 1 and meta.dtype == torch.int64 and meta.dim() == 2 and meta.shape[1] == 6
+    if not meta.is_cuda:
+        meta = meta.to(data.device)
+    n, (H, W) = meta.shape[0], (int(out_hw[0]), int(out_hw[1]))
+    if out is None:
+        out = torch.empty((n, 3, H, W), dtype=dtype, device=data.device)
+    assert out.shape == (n, 3, H, W) and out.dtype == dtype
+    m, s = [float(v) for v in mean], [float(v) for v in std]
+    check(_lib.lib().clipx_image_transform(n, _p(_c(data)), data.numel(), _p(_c(meta)), H, W, m[0], m[1], m[2], s[0], s[1], s[2],
+                                           1 if interpolation == "bicubic" else 0, dt_code(dtype), _p(_c(out)), _stream()))
+    return out
+
+
 @family("embed")
 def vision_assemble(tok, cls, pos, batch, tokens):
     width = tok.shape[-1]

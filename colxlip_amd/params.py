@@ -11,7 +11,7 @@ The flags are a TABLE (`_FLAGS`): name -> argparse keywords.  Three groups:
 import argparse
 import ast
 
-_DATASET_TYPES = ["webdataset", "csv", "synthetic", "auto", "coco", "flickr"]
+_DATASET_TYPES = ["webdataset", "csv", "synthetic", "auto", "coco", "flickr", "packed"]
 _PRECISIONS = ["amp", "amp_bf16", "amp_bfloat16", "bf16", "fp16", "pure_bf16", "pure_fp16", "fp32", "fp8", "fp8_mfma"]
 
 

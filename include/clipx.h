@@ -149,6 +149,21 @@ int clipx_attention_pooled_bwd_split(int dtype, int nseq, int L, int max_len, in
  * columns >= 3*P*P zero-filled (Kp >= 3*P*P; conv1 as GEMM, transformer.py:702-704).     */
 int clipx_patchify(int img_dtype, int dtype, int batch, int H, int W, int P, int Kp,
                    const void* image, void* patches, void* stream);
+/* ---- image input transform (factory.py:411-418 builds open_clip's image_transform_v2 for train and val: torchvision
+ * RandomResizedCrop | Resize + CenterCrop, ToTensor, Normalize on PIL images; the datasets decode with PIL, data.py:732).
+ * bytes: `nbytes` of uint8 HWC RGB images, stored back to back at any offsets.  meta: `batch` records of 48 bytes,
+ *   { int64 offset; int32 h, w, top, left, bh, bw, vh, vw, oy, ox }: image i is bytes[offset, offset + 3*h*w), its source box
+ *   rows top .. top+bh, columns left .. left+bw; (vh, vw) the virtual output size; (oy, ox) the origin of the H x W window of it
+ *   (where the window reaches past the virtual output, out is left untouched).
+ * out[i, c, y, x] (out_dtype, contiguous NCHW) = (level / 255 - mean[c]) / std[c], level = the pixel (oy + y, ox + x), channel c,
+ *   of PIL's Image.resize((vw, vh), BICUBIC if bicubic else BILINEAR) of the boxed region: horizontal pass, round half up and
+ *   clamp to [0, 255], vertical pass, round and clamp, in PIL's 22-bit fixed point (csrc/image_transform.hip).  Train: box = the random crop,
+ *   (vh, vw) = (H, W), origin 0.  Val: box = the image, (vh, vw) = the resized size, window = the centre crop.
+ * Per axis box / virtual size <= 16.  No byte outside an image's [offset, offset + 3*h*w) is read: the box is clamped to the
+ *   image, and a record that breaks a limit leaves its image's output untouched (callers validate first: ops.image_geometry). */
+int clipx_image_transform(int batch, const void* bytes, size_t nbytes, const void* meta, int H, int W, float mean0,
+                          float mean1, float mean2, float std0, float std1, float std2, int bicubic, int out_dtype,
+                          void* out, void* stream);
 /* x0[b, 0] = cls + pos[0]; x0[b, 1+g] = tok[b*G2+g] + pos[1+g]  (transformer.py:707-709)  */
 int clipx_vision_assemble(int dtype, int batch, int tokens, int width, const void* tok,
                           const float* cls, const float* pos, void* x0, void* stream);
