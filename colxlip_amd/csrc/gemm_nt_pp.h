@@ -37,6 +37,7 @@
 #include <type_traits>
 #include "kernels.h"
 #include "gemm_epi.h"
+#include "pp_probe.h"      // PpNoProbe, PP_T_*: the cycle-accounting hooks of the kernel body below
 
 #define PP_X_BYTES (256 * 128)      // 32 KiB: 256 x rows of one k-step
 #define PP_W_BYTES (128 * 128)      // 16 KiB: one group's 128 w rows
@@ -56,15 +57,6 @@ __device__ __forceinline__ void pp_frag_read(FRAG& dst, const unsigned (&wa)[2],
     else
         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(xa[s]), "n"((r - 4) * 2048));
 }
-
-// In-kernel cycle accounting hooks: tick() restarts the clock, lap<I>() charges the time since the last hook to counter I.  This
-// one is the default build's: nothing.  (gemm_bf16_nt8p.hip has the counting one behind -DPP_PROFILE.)
-struct PpNoProbe {
-    __device__ __forceinline__ void tick() {}
-    template <int I> __device__ __forceinline__ void lap() {}
-    __device__ __forceinline__ void flush(int, int) {}
-};
-enum { PP_T_EPI = 1, PP_T_L = 2, PP_T_LWAIT = 3, PP_T_C = 4, PP_T_VMCNT = 5, PP_T_CBAR = 6 };
 
 // The kernel body.  T: typedef elem (1 or 2 bytes; a k-step is 128 / sizeof(elem) elements) and frag (16 bytes); chunk(ks, g):
 // the 16-byte chunk of a row that lane group g reads into slice ks; mfma<FIRST>(acc, F): the C segment.  tail(acc, m0, n0, wm,

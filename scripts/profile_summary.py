@@ -20,7 +20,7 @@ FAMILIES = [
     ("NT one-barrier", r"gemm_bf16_nt_kernel"),
     ("NT fp8", r"gemm_fp8_nt8p_kernel"),
     ("TN wgrad", r"gemm_bf16_tn"),
-    ("TN slab / partial reduce", r"slab_reduce_kernel|reduce_partials"),
+    ("TN slab / partial reduce", r"slab_reduce_(group_)?kernel|reduce_partials"),
     ("attention fwd", r"attn_\w*fwd"),
     ("attention bwd", r"attn_\w*bwd"),
     ("LayerNorm fwd", r"ln_fwd"),
