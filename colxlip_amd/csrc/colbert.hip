@@ -164,7 +164,7 @@ extern "C" int clipx_maxsim_scatter(int dtype, int ct, int n_tok, int groups, in
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Fused MaxSim (round 4; bf16 tokens, q >= 64).  Three ideas, each exact:
+// Fused MaxSim (round 4; bf16 tokens, q >= 16).  Three ideas, each exact:
 //  (1) DUPLICATE TEXT ROWS ARE COMPUTED ONCE.  Every text position at or behind a caption's EOT leaves ColXLIP's token head as
 //      the SAME vector (reference model.py:589-603 zeroes the token BEFORE the head), so the trailing rows of a sample that are
 //      bitwise equal to its last row have the same similarities, the same maximum and the same arg-max: one representative row
@@ -231,19 +231,28 @@ __global__ __launch_bounds__(256) void maxsim_pack_kernel(int nt, int n_tok, int
     }
 }
 
-// Fold the slot partials of image k for packed row r: maxvT[k, r], argT[k, r] (row-contiguous, like the partials)
+// The partial rows that hold image k, in column order (gemm_nt_maxsim.h): from 64 tokens per image up one row per 64-column slot
+// the image touches, [2 * slot + seg] with seg = 1 when the slot begins inside an earlier image; below that one row per slot
+// half, [2 * k + half].  part = 0 .. maxsim_parts(q, k) - 1.
+__device__ __forceinline__ int maxsim_parts(int q, int k) { return ((((k + 1) * q - 1) >> 6) - ((k * q) >> 6)) + 1; }
+__device__ __forceinline__ int maxsim_part_row(int q, int k, int part) {
+    if (q < 64) return 2 * k + part;
+    const int s = ((k * q) >> 6) + part;
+    return 2 * s + (((s << 6) / q == k) ? 0 : 1);
+}
+
+// Fold the partials of image k for packed row r: maxvT[k, r], argT[k, r] (row-contiguous, like the partials)
 __global__ __launch_bounds__(256) void maxsim_finish_kernel(int R, int ldp, int r0, int ld, int ni, int q, const float* __restrict__ pmax,
                                                             const unsigned short* __restrict__ pidx, float* __restrict__ maxvT,
                                                             unsigned short* __restrict__ argT) {
     const int r = blockIdx.x * 256 + threadIdx.x;        // row inside this chunk of packed rows (partials are per chunk)
     const int k = blockIdx.y;
     if (r >= R) return;
-    const int s_lo = (k * q) >> 6, s_hi = ((k + 1) * q - 1) >> 6;
+    const int parts = maxsim_parts(q, k);
     float best = -INFINITY;
     int bi = 0;
-    for (int s = s_lo; s <= s_hi; ++s) {
-        const int seg = ((s << 6) / q == k) ? 0 : 1;
-        const long o = (long)(2 * s + seg) * ldp + r;
+    for (int p = 0; p < parts; ++p) {
+        const long o = (long)maxsim_part_row(q, k, p) * ldp + r;
         const float v = pmax[o];
         if (v > best) { best = v; bi = pidx[o]; }
     }
@@ -274,7 +283,7 @@ __global__ __launch_bounds__(256) void maxsim_mean_kernel(int nt, int ni, int ld
 // Forward-only scoring (retrieval, ColXLIP.get_logits under no_grad): slot partials -> final scores in one pass, with neither
 // maxvT / argT nor inv_count in memory.  For text samples m < nm (packed rows cu[m] .. cu[m+1], chunk-local row = r - rbase) and
 // images k < ni of the partial arrays' image chunk:
-//     tok[m, k]    = sum_r w_r v_r / (sum_r w_r [v_r != 0] + 1e-8),  v_r = max over the slot segments of image k (as finish)
+//     tok[m, k]    = sum_r w_r v_r / (sum_r w_r [v_r != 0] + 1e-8),  v_r = max over the partials of image k (as finish)
 //     scores[k, m] = scale * (alpha * G[k, m] + beta * tok[m, k]),  beta = 1 - alpha   (image-major; G == nullptr: no global term)
 // The partials are row-contiguous and a sample's rows are consecutive, so a wave owns one image and walks SPW consecutive
 // samples with its lanes on consecutive rows (256-byte reads per segment; > 64 rows take another pass) and reduces (sum,
@@ -292,15 +301,14 @@ __global__ __launch_bounds__(256) void maxsim_score_fold_kernel(int nm, int ni, 
     const int mcnt = min(MAXSIM_FOLD_SPW, nm - mb);
     float tok = 0.f;
     if (pmax) {
-        const int s_lo = (k * q) >> 6, s_hi = ((k + 1) * q - 1) >> 6;
+        const int parts = maxsim_parts(q, k);
         for (int i = 0; i < mcnt; ++i) {
             const int ra = cu[mb + i] - rbase, rb = cu[mb + i + 1] - rbase;
             float s = 0.f, c = 0.f;
             for (int r = ra + lane; r < rb; r += 64) {
                 float best = -INFINITY;
-                for (int sl = s_lo; sl <= s_hi; ++sl) {
-                    const int seg = ((sl << 6) / q == k) ? 0 : 1;
-                    const float v = pmax[(long)(2 * sl + seg) * ldp + r];
+                for (int p = 0; p < parts; ++p) {
+                    const float v = pmax[(long)maxsim_part_row(q, k, p) * ldp + r];
                     best = v > best ? v : best;
                 }
                 const float w = row_w[rbase + r];
@@ -390,10 +398,11 @@ extern "C" int clipx_maxsim_pack_rows(int nt, int n_tok, int e, const void* txt,
     return 0;
 }
 
-// partial maxima of S = packed . img^T per (row, 64-column slot, segment): pmax / pidx are [2 * ceil(ni*q / 64), ld]
+// partial maxima of S = packed . img^T: per (row, 64-column slot, segment) from 64 tokens per image up, pmax / pidx
+// [2 * ceil(ni*q / 64), ld]; per (row, image, slot half) for 16 <= q < 64, [2 * ni, ld]
 extern "C" int clipx_maxsim_gemm(int R, int ni, int q, int e, const void* packed, const void* img, float* pmax,
                                  unsigned short* pidx, int ld, void* stream) {
-    CLIPX_CHECK(q >= 64 && q <= 65535 && e % 64 == 0 && e >= 128 && ld >= R, "maxsim_gemm: needs q >= 64, embed dim %% 64 == 0 (q=%d e=%d)", q, e);
+    CLIPX_CHECK(q >= 16 && q <= 65535 && e % 64 == 0 && e >= 128 && ld >= R, "maxsim_gemm: needs q >= 16, embed dim %% 64 == 0 (q=%d e=%d)", q, e);
     if (R <= 0 || ni <= 0) return 0;
     EpiB16 epi = {};
     epi.ms_max = pmax;
@@ -418,7 +427,7 @@ extern "C" int clipx_maxsim_score_fold(int nm, int ni, int q, int ldp, int rbase
                                        const float* G, long ld_g, float* scores, long ld_scores, float alpha, float beta, float scale,
                                        void* stream) {
     CLIPX_CHECK(pmax || G, "maxsim_score_fold: the global-only form (no partials) needs G");
-    CLIPX_CHECK(!pmax || (q >= 64 && ldp >= 1 && cu && row_w), "maxsim_score_fold: partials need q >= 64, cu and row_w (q=%d)", q);
+    CLIPX_CHECK(!pmax || (q >= 16 && ldp >= 1 && cu && row_w), "maxsim_score_fold: partials need q >= 16, cu and row_w (q=%d)", q);
     CLIPX_CHECK(ni <= 4 * 65535, "maxsim_score_fold: at most 262140 images per call (got %d)", ni);
     if (nm <= 0 || ni <= 0) return 0;
     hipLaunchKernelGGL(maxsim_score_fold_kernel, dim3(cdiv(nm, MAXSIM_FOLD_SPW), cdiv(ni, 4)), dim3(256), 0, (hipStream_t)stream, nm, ni,

@@ -73,7 +73,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt8p_kernel(int M, int N, in
                                                                 OUT_T* __restrict__ out, int tiles_m, int tiles_n, int gm) {
     pp_gemm_nt<PpBf16>(M, N, K, X, W, tiles_m, tiles_n, gm,
                        [&](f32x4 (&acc)[4][8], int m0, int n0, int wm, int wn, int lane) {
-                           if constexpr ((FL & F_MAXSIM) != 0)
+                           if constexpr ((FL & F_MAXSIM_SEG) != 0)
+                               nt_maxsim_seg_epilogue<8>(acc, epi, M, N, m0, n0, wm, wn, lane);
+                           else if constexpr ((FL & F_MAXSIM) != 0)
                                nt_maxsim_epilogue<8>(acc, epi, M, N, m0, n0, wm, wn, lane);
                            else
                                (void)nt_tile_epilogue<OUT_T, 8, FL, ACT>(acc, epi, out, M, N, m0, n0, wm, wn, lane);
@@ -87,9 +89,12 @@ static int launch_pp(int M, int N, int K, const bf16_t* X, const bf16_t* W, cons
     return pp_launch<gemm_bf16_nt8p_kernel<bf16_t, FL, ACT>>(M, N, K, X, W, epi, out, n_cu, stream);
 }
 
-// S = X . W^T reduced on the fly to per-(row, slot, segment) maxima (gemm_nt_maxsim.h); nothing else is written
+// S = X . W^T reduced on the fly to per-(row, slot, segment) maxima, per-(row, image, half) below 64 tokens per image
+// (gemm_nt_maxsim.h); nothing else is written
 int launch_gemm_bf16_nt8p_maxsim(int M, int N, int K, const bf16_t* X, const bf16_t* W, const EpiB16& epi, hipStream_t stream) {
-    if (K % 64 != 0 || K < 128 || (long)256 * K * 2 >= (1l << 31) || epi.ms_q < 64 || epi.ms_q > 65535) return 1;
+    if (K % 64 != 0 || K < 128 || (long)256 * K * 2 >= (1l << 31) || epi.ms_q < 16 || epi.ms_q > 65535) return 1;
+    if (epi.ms_q < 64)
+        return launch_pp<F_MAXSIM | F_MAXSIM_SEG, CLIPX_ACT_NONE>(M, N, K, X, W, epi, nullptr, clipx_num_cu(false), stream);
     return launch_pp<F_MAXSIM, CLIPX_ACT_NONE>(M, N, K, X, W, epi, nullptr, clipx_num_cu(false), stream);
 }
 

@@ -5,7 +5,8 @@
 #include <type_traits>
 #include "kernels.h"
 
-enum { F_BIAS = 1, F_RES = 2, F_ACTU = 4, F_ACT = 8, F_PRE = 16, F_MAXSIM = 32, F_PRE8 = 64, F_ACTU8 = 128 };
+enum { F_BIAS = 1, F_RES = 2, F_ACTU = 4, F_ACT = 8, F_PRE = 16, F_MAXSIM = 32, F_PRE8 = 64, F_ACTU8 = 128,
+       F_MAXSIM_SEG = 256 };   // with F_MAXSIM: the per-image form for fewer than 64 tokens per image (gemm_nt_maxsim.h)
 
 // GELU'(u) on EIGHT bits (round 4).  What the c_fc epilogue costs beyond its bias form is not the polynomial but the second
 // store -- fc bias 0.896 ms, + GELU 0.939, + bf16 pre-activation store 1.051 (scripts/bench_epi.py, ViT-B/32 vision shape at

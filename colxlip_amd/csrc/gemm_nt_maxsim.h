@@ -83,3 +83,59 @@ __device__ __forceinline__ void nt_maxsim_epilogue(f32x4 (&acc)[4][MT], const Ep
         }
     }
 }
+
+// 16 <= q < 64: the slot's images kA, kA + 1, ... one at a time.  Segment s holds the relative columns
+// max(0, bnd_{s-1}) <= r < min(64, bnd_s) with bnd_s = (kA + 1 + s) * q - col0 (bnd_{-1} <= 0: image kA began in an earlier slot
+// when it is negative).  Same tie rules as above: a larger value wins, the smaller column on equal values.
+template <int MT>
+__device__ __forceinline__ void nt_maxsim_seg_epilogue(f32x4 (&acc)[4][MT], const EpiB16& epi, int M, int N, int m0, int n0, int wm,
+                                                       int wn, int lane) {
+    const int g = lane >> 4, c = lane & 15;
+    const int q = epi.ms_q;
+    const int col0 = n0 + wn * 64;                       // wave-uniform
+    if (col0 >= N) return;
+    const int kA = col0 / q;
+    const int row0 = m0 + wm * 16 * MT + c;
+#pragma unroll 1
+    for (int k = kA, start = kA * q - col0; start < 64 && col0 + start < N; ++k, start += q) {
+        const int lo = start < 0 ? 0 : start;            // start: relative column of the image's token 0
+        const int hi = start + q < 64 ? start + q : 64;
+        const long o = (long)(2 * k + (start < 0 ? 1 : 0)) * epi.ms_ld;
+        float* pm = epi.ms_max + o;
+        unsigned short* pi = epi.ms_idx + o;
+#pragma unroll
+        for (int j = 0; j < MT; ++j) {
+            float m = -INFINITY;
+            int idx = 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (16 * i + 16 <= lo || 16 * i >= hi) continue;       // wave-uniform: a 16-column block outside the segment
+                if (16 * i >= lo && 16 * i + 16 <= hi) {               // ... wholly inside: no mask
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float v = acc[i][j][e];
+                        if (v > m) { m = v; idx = 16 * i + 4 * g + e; }
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int r = 16 * i + 4 * g + e;
+                        const float v = (r >= lo && r < hi) ? acc[i][j][e] : -INFINITY;
+                        if (v > m) { m = v; idx = r; }
+                    }
+                }
+            }
+#pragma unroll
+            for (int w = 16; w <= 32; w <<= 1) {
+                const float om = __shfl_xor(m, w, 64);
+                const int oi = __shfl_xor(idx, w, 64);
+                if (om > m || (om == m && oi < idx)) { m = om; idx = oi; }
+            }
+            const int row = row0 + 16 * j;
+            if (g == 0 && row < M) {
+                pm[row] = m;
+                pi[row] = (unsigned short)(idx - start);
+            }
+        }
+    }
+}

@@ -19,9 +19,10 @@ struct EpiB16 {
     int act_u_kind;
     const bf16_t* residual;   // optional [M,N]
     // MaxSim epilogue (gemm_nt_maxsim.h): no output tile; per (row, 64-column slot, segment) maximum + index inside the image
-    float* ms_max;            // [2 * slots, ms_ld]
-    unsigned short* ms_idx;   // [2 * slots, ms_ld]
-    int ms_q, ms_ld;          // tokens per image (>= 64), row stride of the two arrays
+    // (per (row, image, slot half) below 64 tokens per image)
+    float* ms_max;            // [2 * slots, ms_ld]   (ms_q < 64: [2 * images, ms_ld])
+    unsigned short* ms_idx;   // the same shape
+    int ms_q, ms_ld;          // tokens per image (>= 16), row stride of the two arrays
     // GELU'(pre-activation) on eight bits (gemm_epi.h, G8_*): written by the c_fc epilogue, read by the c_proj dgrad epilogue
     unsigned char* pre8;          // optional [M,N]
     const unsigned char* actu8;   // optional [M,N]

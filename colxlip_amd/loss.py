@@ -410,8 +410,9 @@ class _MaxSimLogits(torch.autograd.Function):
 
 
 class _MaxSimFused(torch.autograd.Function):
-    """compute_colbert_similarity for bf16 token features with >= 64 tokens per image -- the fork's own operating point
-    (ViT-B-16-colxlip: 196 image tokens; reference src/colxlip.sh: 512 pairs per GPU, global logits on every rank) -- with
+    """compute_colbert_similarity for bf16 token features with >= 16 tokens per image -- the fork's own operating points
+    (ViT-B-16-colxlip: 196 image tokens, ViT-B-32-colxlip: 49; reference src/colxlip.sh: 512 pairs per GPU, global logits on
+    every rank) -- with
     neither the [Nt, Ni, n, q] tensor of the reference's einsum nor the [Nt n, Ni q] similarity matrix of `_MaxSimLogits` in
     memory (csrc/colbert.hip "Fused MaxSim", csrc/gemm_nt_maxsim.h):
       * trailing text positions of a sample that are bitwise equal to its last position -- every position at or behind the EOT
@@ -430,7 +431,7 @@ class _MaxSimFused(torch.autograd.Function):
     @staticmethod
     def applies(tok_img, tok_txt) -> bool:
         ni, q, e = tok_img.shape
-        return (tok_txt.dtype == torch.bfloat16 and tok_img.dtype == torch.bfloat16 and tok_txt.is_cuda and 64 <= q <= 65535
+        return (tok_txt.dtype == torch.bfloat16 and tok_img.dtype == torch.bfloat16 and tok_txt.is_cuda and 16 <= q <= 65535
                 and e % 64 == 0 and e >= 128 and (ni * q) % 8 == 0 and os.environ.get("CLIPX_MAXSIM_FUSED", "1") != "0")
 
     @staticmethod
@@ -455,16 +456,17 @@ class _MaxSimFused(torch.autograd.Function):
         cu, R = ops.maxsim_pack_text(txt)
         packed, row_m, row_w = ops.maxsim_pack_rows(txt, cu, R)
         ld = (R + 255) // 256 * 256
-        slots = (ni * q + 63) // 64
+        prow = ops.maxsim_partial_rows(ni, q)
         maxvT = torch.empty((ni, ld), dtype=torch.float32, device=dev)
         argT = torch.empty((ni, ld), dtype=torch.int16, device=dev)
-        # partial maxima: 6 bytes per (row, slot, segment); rows in chunks when that would pass CHUNK_BYTES
-        rows_per = max(256, (_MaxSimFused.CHUNK_BYTES // (12 * slots)) // 256 * 256)
+        # partial maxima: 6 bytes per (row, slot, segment) -- per (row, image, slot half) below 64 tokens per image; rows in
+        # chunks when that would pass CHUNK_BYTES
+        rows_per = max(256, (_MaxSimFused.CHUNK_BYTES // (6 * prow)) // 256 * 256)
         for r0 in range(0, R, rows_per):
             rc = min(rows_per, R - r0)
             ldp = (rc + 255) // 256 * 256
-            pmax = torch.empty((2 * slots, ldp), dtype=torch.float32, device=dev)
-            pidx = torch.empty((2 * slots, ldp), dtype=torch.int16, device=dev)
+            pmax = torch.empty((prow, ldp), dtype=torch.float32, device=dev)
+            pidx = torch.empty((prow, ldp), dtype=torch.int16, device=dev)
             ops.maxsim_gemm(packed[r0:r0 + rc], img, ni, q, pmax, pidx, ldp)
             ops.maxsim_finish(rc, ldp, r0, ld, ni, q, pmax, pidx, maxvT, argT)
             del pmax, pidx

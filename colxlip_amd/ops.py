@@ -890,7 +890,7 @@ def maxsim_scatter(dlogits, inv_count, arg, n_tok, q, dtype, want_transpose):
     return P, PT
 
 
-# fused form (bf16 tokens, >= 64 tokens per image): include/clipx.h "Fused MaxSim"
+# fused form (bf16 tokens, >= 16 tokens per image): include/clipx.h "Fused MaxSim"
 def maxsim_pack_text(txt):
     """txt [nt, n, e] bf16 -> (cu int32 [nt+1] on the device, R = packed rows; one 4-byte read-back).  Trailing positions of a
     sample that are bitwise equal to its last position are folded into one representative row."""
@@ -966,9 +966,16 @@ def maxsim_partial_ld(rows: int) -> int:
     return (rows + 15) // 16 * 16
 
 
+def maxsim_partial_rows(ci: int, q: int) -> int:
+    """rows of the partial arrays of `ci` images (csrc/gemm_nt_maxsim.h): two segments per 64-column slot from 64 tokens per
+    image up, two slot halves per image below that"""
+    return 2 * ci if q < 64 else 2 * ((ci * q + 63) // 64)
+
+
 def maxsim_partial_bytes(ci: int, q: int, rows: int) -> int:
-    """pmax (fp32) + pidx (int16) of `ci` images against `rows` packed rows: 6 bytes per (row, 64-column slot, segment)"""
-    return 12 * ((ci * q + 63) // 64) * maxsim_partial_ld(rows)
+    """pmax (fp32) + pidx (int16) of `ci` images against `rows` packed rows: 6 bytes per (row, 64-column slot, segment), per
+    (row, image, slot half) below 64 tokens per image"""
+    return 6 * maxsim_partial_rows(ci, q) * maxsim_partial_ld(rows)
 
 
 def plan_maxsim_chunks(ni, q, e, cu_host, partial_bytes, operand_bytes=None):
@@ -986,15 +993,15 @@ def plan_maxsim_chunks(ni, q, e, cu_host, partial_bytes, operand_bytes=None):
     nt = len(cu_host) - 1
     unit = 8 // math.gcd(q, 8)                                   # image counts with (ci * q) % 8 == 0
     want_ld = maxsim_partial_ld(max(1, min(MAXSIM_TARGET_ROWS, cu_host[nt])))
-    cmax = min(MAXSIM_MAX_IMAGES, operand_bytes // (2 * q * e), (partial_bytes // (12 * want_ld)) * 64 // q)
+    fit = partial_bytes // (12 * want_ld)                        # slots (q >= 64) or images whose partials fit
+    cmax = min(MAXSIM_MAX_IMAGES, operand_bytes // (2 * q * e), fit if q < 64 else fit * 64 // q)
     cmax = max(unit, cmax // unit * unit)
     cmax = min(cmax, (ni + unit - 1) // unit * unit)
     image_chunks = []
     for k0 in range(0, ni, cmax):
         k1 = min(ni, k0 + cmax)
         image_chunks.append((k0, k1, (k1 - k0 + unit - 1) // unit * unit))
-    slots = (cmax * q + 63) // 64
-    limit_rows = partial_bytes // (12 * slots) // 16 * 16
+    limit_rows = partial_bytes // (6 * maxsim_partial_rows(cmax, q)) // 16 * 16
     text_chunks, m0 = [], 0
     while m0 < nt:
         m1 = m0 + 1
@@ -1021,7 +1028,7 @@ def maxsim_score_fold(nm, ni, q, ldp, rbase, cu, m0, row_w, pmax, G, scores, alp
 def maxsim_fused_applies(tok_img, tok_txt) -> bool:
     """the shapes `_MaxSimFused.applies` takes, without its image-count alignment (the chunk plan pads the last chunk)"""
     ni, q, e = tok_img.shape
-    return (tok_txt.dtype == torch.bfloat16 and tok_img.dtype == torch.bfloat16 and tok_txt.is_cuda and 64 <= q <= 65535
+    return (tok_txt.dtype == torch.bfloat16 and tok_img.dtype == torch.bfloat16 and tok_txt.is_cuda and 16 <= q <= 65535
             and e % 64 == 0 and e >= 128 and os.environ.get("CLIPX_MAXSIM_FUSED", "1") != "0")
 
 
@@ -1036,9 +1043,9 @@ def _maxsim_scores_fused(tok_img, tok_txt, G, alpha, scale, out):
     image_chunks, text_chunks = plan_maxsim_chunks(ni, q, e, cu.cpu().tolist(), _MaxSimFused.CHUNK_BYTES)
     cmax = max(c for _, _, c in image_chunks)
     ldmax = maxsim_partial_ld(max(r1 - r0 for _, _, r0, r1 in text_chunks))
-    slots = (cmax * q + 63) // 64
-    pmax = torch.empty((2 * slots * ldmax,), dtype=torch.float32, device=dev)
-    pidx = torch.empty((2 * slots * ldmax,), dtype=torch.int16, device=dev)
+    prow = maxsim_partial_rows(cmax, q)
+    pmax = torch.empty((prow * ldmax,), dtype=torch.float32, device=dev)
+    pidx = torch.empty((prow * ldmax,), dtype=torch.int16, device=dev)
     for k0, k1, ci in image_chunks:
         if ci == k1 - k0:
             op = img[k0 * q:k1 * q]
@@ -1084,8 +1091,8 @@ def maxsim_scores(tok_img, tok_txt, G, alpha, scale, out=None):
     """Late-interaction scores without autograd: scores [ni, nt] (fp32, image-major) =
         scale * (alpha * G + (1 - alpha) * MaxSim(tok_img [ni, q, e], tok_txt [nt, n, e])^T)
     with MaxSim the reference's compute_colbert_similarity (loss.py:20-46) and G [ni, nt] the fp32 global similarities (None:
-    no global term).  bf16 tokens with q >= 64 and e % 64 == 0 go through the MaxSim GEMM and `clipx_maxsim_score_fold` per
-    (image chunk x text chunk): nothing of size rows x images is kept.  Everything else (fp32 tokens, q < 64, other embed dims)
+    no global term).  bf16 tokens with q >= 16, e % 64 == 0 and e >= 128 go through the MaxSim GEMM and `clipx_maxsim_score_fold` per
+    (image chunk x text chunk): nothing of size rows x images is kept.  Everything else (fp32 tokens, q < 16, other embed dims)
     runs in fp32 on gemm_f32 + maxsim_reduce + masked_mean.  alpha = 1 is scale * G bit for bit: no token kernel runs and the
     token features are not looked at (they may be None)."""
     alpha, scale = float(alpha), float(scale)

@@ -432,13 +432,14 @@ int clipx_linear_fwd_fp8_gelu8(int M, int N, int K, const void* x8, const int* x
 int clipx_linear_dgrad_fp8_gelu8(int M, int N, int K, const void* dy8, const int* dy_exp, const void* wt8, const int* wt_exp,
                                  const void* g8, void* dx, void* stream);
 
-/* Fused MaxSim for bf16 token features with >= 64 tokens per image (csrc/colbert.hip, csrc/gemm_nt_maxsim.h; replaces the
+/* Fused MaxSim for bf16 token features with >= 16 tokens per image (csrc/colbert.hip, csrc/gemm_nt_maxsim.h; replaces the
  * einsum + max + masked mean of reference loss.py:20-46 without the similarity tensor in memory).
  * pack_text: cnt[m] = number of packed rows of sample m (its leading rows + ONE representative of the trailing rows that are
  *   bitwise equal to its last row), cu = exclusive scan (cu[nt] = packed rows in total).  pack_rows: packed [R, e] bf16,
  *   row_m[r] = sample, row_w[r] = how many original positions the row stands for.
  * gemm: S = packed . img^T reduced in the GEMM epilogue to per-(row, 64-column slot, segment) maxima: pmax / pidx are
- *   [2 * ceil(ni*q/64), ldp] (ldp >= R).  finish: folds an image's slots (first maximum wins) into maxvT / argT [ni, ld] at
+ *   [2 * ceil(ni*q/64), ldp] (ldp >= R); for 16 <= q < 64 to per-(row, image, slot half) maxima, [2 * ni, ldp].
+ *   finish: folds an image's partials in column order (first maximum wins) into maxvT / argT [ni, ld] at
  *   rows r0 .. r0+R.  mean: logits[m,k] = sum_r w_r maxvT[k,r] / (sum_r w_r [maxvT != 0] + 1e-8), inv_count = 1 / that denominator.
  * scatter_packed: P[r - r0, k*q + qq] = (qq == argT[k,r]) ? dlogits[m_r,k] * inv_count[m_r,k] : 0 (bf16) for rows r0 .. r0+R.
  * scale_rows: y[r,:] = w_r x[r,:].  expand: dtxt[m, n, :] = dpacked[cu[m] + min(n, cnt[m]-1), :].                        */
