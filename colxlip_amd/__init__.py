@@ -9,3 +9,11 @@ from .model import get_model_tokenize_cfg, get_model_preprocess_cfg, set_model_p
 from . import ops
 
 __version__ = "0.3.0"
+
+
+def __getattr__(name):
+    # resolved on first use: `python -m colxlip_amd.search` must not find its own module imported already
+    if name == "LateInteractionIndex":
+        from .search import LateInteractionIndex
+        return LateInteractionIndex
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

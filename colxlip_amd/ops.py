@@ -1119,3 +1119,33 @@ def maxsim_scores(tok_img, tok_txt, G, alpha, scale, out=None):
         if maxsim_fused_applies(tok_img, tok_txt):
             return _maxsim_scores_fused(tok_img.detach(), tok_txt.detach(), G, alpha, scale, out)
         return _maxsim_scores_general(tok_img.detach(), tok_txt.detach(), G, alpha, scale, out)
+
+
+# ------------------------------------------------------------------ streaming top-k (late-interaction search)
+TOPK_MAX_K = 256
+
+
+def topk_init(nq, k, device):
+    """Empty running lists of `topk_merge`: (best_val [nq, k] fp32 of -inf, best_idx [nq, k] int32 of -1)."""
+    if not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f"topk_init: k must be in 1 .. {TOPK_MAX_K} (got {k})")
+    return (torch.full((nq, k), float("-inf"), dtype=torch.float32, device=device),
+            torch.full((nq, k), -1, dtype=torch.int32, device=device))
+
+
+def topk_merge(scores, query_dim, c_base, best_val, best_idx):
+    """One step of the running selection (`clipx_topk_merge`): `scores` is a 2-D fp32 view whose dimension `query_dim` (0 or 1)
+    indexes the queries and whose other dimension indexes gallery positions c_base, c_base + 1, ...; one of its strides must
+    be 1.  best_val / best_idx [nq, k] are updated in place: the k best under (larger value, then smaller position)."""
+    assert query_dim in (0, 1) and scores.dim() == 2 and scores.dtype == torch.float32
+    nq, nc = scores.shape[query_dim], scores.shape[1 - query_dim]
+    qs, cs = scores.stride(query_dim), scores.stride(1 - query_dim)
+    if nq == 1 and nc > 1:                                       # the stride of a dimension of one element says nothing
+        qs = 1 if cs != 1 else max(2, nc)
+    elif nc == 1 and nq > 1:
+        cs = 1 if qs != 1 else max(2, nq)
+    k = best_val.shape[1] if best_val.dim() == 2 else 0
+    assert best_val.shape == (nq, k) and best_idx.shape == (nq, k)
+    assert best_val.dtype == torch.float32 and best_idx.dtype == torch.int32
+    check(_lib.lib().clipx_topk_merge(nq, nc, k, _p(scores), qs, cs, int(c_base), _p(_c(best_val)), _p(_c(best_idx)), _stream()))
+    return best_val, best_idx

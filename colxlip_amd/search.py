@@ -1,0 +1,431 @@
+"""Late-interaction search: the k best gallery items per query, without the dense score matrix.
+
+`LateInteractionIndex` owns the features of one side (the gallery) on the device.  `search` walks (query chunk x gallery chunk):
+the global similarities of the pair are one fp32 GEMM (`train.similarity_matrix`), `ops.maxsim_scores` writes the pair's score
+tile into a buffer that is allocated once per search, and `ops.topk_merge` (`clipx_topk_merge`, csrc/topk.hip) folds the tile into
+the running k best of every query.  The scores are those of `ColXLIP.get_logits` / `train.evaluate` (the reference's
+arithmetic); the selection replaces the reference's per-row CPU argsort (train.py:457-508), which needs every score in memory.
+
+    python -m colxlip_amd.search --model NAME [--pretrained CKPT] [--precision bf16] --dataset-type synthetic|packed
+        [--val-data DIR] --retrieval-coco --direction t2i|i2t --k 10 --out results.npz [--save-index DIR | --load-index DIR]
+"""
+import json
+import logging
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import ops
+
+_FILES = ("meta.json", "features.npy", "tokens.npy", "ids.npy")
+
+
+def topk_reference(scores, k, query_dim, c_base=0, best=None):
+    """The selection of `ops.topk_merge` in plain torch, on the CPU: (values [nq, k] fp32, positions [nq, k] int32) of the k best
+    candidates per query under (larger value first, then smaller gallery position), by stable sorts.  `scores` is 2-D, dimension
+    `query_dim` indexes the queries and the other one gallery positions c_base, c_base + 1, ...; -inf and NaN candidates are
+    skipped, missing entries are (-inf, -1).  `best` = (values, positions) of an earlier call joins the candidates."""
+    s = scores.detach().cpu().float()
+    s = s if query_dim == 0 else s.t()
+    nq, nc = s.shape
+    val = s.clone()
+    pos = (torch.arange(nc, dtype=torch.int64) + int(c_base)).expand(nq, nc).clone()
+    if best is not None:
+        val = torch.cat([best[0].detach().cpu().float(), val], dim=1)
+        pos = torch.cat([best[1].detach().cpu().to(torch.int64), pos], dim=1)
+    dead = torch.isnan(val) | (val == float("-inf"))
+    val[dead] = float("-inf")
+    pos[dead] = -1
+    order = torch.sort(pos, dim=1, stable=True)[1]                       # smaller position first ...
+    val, pos = val.gather(1, order), pos.gather(1, order)
+    order = torch.sort(val, dim=1, descending=True, stable=True)[1]      # ... among equal values
+    val, pos = val.gather(1, order), pos.gather(1, order)
+    out_v = torch.full((nq, k), float("-inf"), dtype=torch.float32)
+    out_i = torch.full((nq, k), -1, dtype=torch.int32)
+    m = min(k, val.shape[1])
+    out_v[:, :m] = val[:, :m]
+    out_i[:, :m] = pos[:, :m].to(torch.int32)
+    return out_v, out_i
+
+
+def image_chunk_items(limit, q):
+    """Images per chunk of the scorer's image operand: at most `limit` and `ops.MAXSIM_MAX_IMAGES`, a multiple of the unit that
+    makes (ci * q) % 8 == 0 (the MaxSim GEMM's alignment), so that only a last, partial chunk is ever padded."""
+    unit = 8 // math.gcd(int(q), 8)
+    return max(unit, min(int(limit), ops.MAXSIM_MAX_IMAGES) // unit * unit)
+
+
+def _to_numpy(t):
+    """(array, dtype name): bf16 travels as its uint16 bit patterns"""
+    t = t.detach().cpu().contiguous()
+    if t.dtype == torch.bfloat16:
+        return t.view(torch.int16).numpy().view(np.uint16), "bfloat16"
+    return t.numpy(), str(t.dtype).replace("torch.", "")
+
+
+def _from_numpy(a, dtype_name):
+    a = np.array(a)                                  # a writable copy (the source may be a read-only memory map)
+    if dtype_name == "bfloat16":
+        return torch.from_numpy(a.view(np.int16)).view(torch.bfloat16)
+    return torch.from_numpy(a)
+
+
+class LateInteractionIndex:
+    """A gallery of images (`kind="image"`, queried with texts) or of texts (`kind="text"`, queried with images), scored by
+        scale * (alpha * global + (1 - alpha) * MaxSim(tokens))
+    as `ops.maxsim_scores` computes it.  `prescale` moves the scale onto the image features BEFORE the similarity GEMM,
+    (scale * I) T^T, which is how a plain CLIP model forms its logits (reference train.py:608); it needs alpha = 1.
+    A model's logit_bias is not part of the scores: a constant does not change a ranking."""
+
+    CHUNK_ITEMS = 16384          # gallery items per chunk (storage and scoring)
+    QUERY_CHUNK = 8192           # queries per chunk: the score tile is at most CHUNK_ITEMS x QUERY_CHUNK x 4 bytes
+    IO_ITEMS = 65536             # items per copy of save / load
+
+    def __init__(self, kind="image", alpha=0.5, scale=1.0, device="cuda", prescale=False):
+        if kind not in ("image", "text"):
+            raise ValueError(f"LateInteractionIndex: kind must be 'image' or 'text' (got {kind!r})")
+        if prescale and float(alpha) != 1.0:
+            raise ValueError("LateInteractionIndex: prescale is the plain CLIP form of the logits and needs alpha = 1")
+        self.kind, self.alpha, self.scale, self.prescale = kind, float(alpha), float(scale), bool(prescale)
+        self.device = torch.device(device)
+        self._feat, self._tok = [], []           # chunks [chunk, E] fp32 / [chunk, q, E]; the last one may be partly filled
+        self._ids = torch.empty((0,), dtype=torch.int64, device=self.device)      # capacity doubles
+        self._n = 0
+        self._chunk = None                       # items per chunk, fixed by the first add
+        self._running_ids = True                 # ids are the positions: search skips the gather
+
+    def __len__(self):
+        return self._n
+
+    @property
+    def has_tokens(self):
+        return bool(self._tok)
+
+    @property
+    def ids(self):
+        return self._ids[:self._n]
+
+    # ------------------------------------------------------------------ storage
+    def _plan_chunk(self, tokens):
+        if self.kind == "image" and tokens is not None:
+            return image_chunk_items(self.CHUNK_ITEMS, tokens.shape[1])
+        return max(1, int(self.CHUNK_ITEMS))
+
+    def add(self, features, tokens=None, ids=None):
+        """features [n, E] fp32, normalised; tokens [n, q, E] in the model's compute dtype (None: a model without token features,
+        alpha must be 1); ids int64 [n] (default: the running position).  Storage grows by chunks of `CHUNK_ITEMS` items; only the
+        last, partly filled chunk is ever copied (it doubles up to a full chunk)."""
+        n = features.shape[0]
+        if features.dim() != 2 or features.dtype != torch.float32:
+            raise ValueError("LateInteractionIndex.add: features must be [n, E] fp32")
+        if self.alpha == 1.0:
+            tokens = None                        # never read
+        elif tokens is None:
+            raise ValueError("LateInteractionIndex.add: alpha != 1 scores with token features; pass tokens or use alpha = 1")
+        if tokens is not None and (tokens.dim() != 3 or tokens.shape[0] != n or tokens.shape[2] != features.shape[1]):
+            raise ValueError("LateInteractionIndex.add: tokens must be [n, q, E] with the features' n and E")
+        if self._n and tokens is not None and (tokens.shape[1:] != self._tok[0].shape[1:] or tokens.dtype != self._tok[0].dtype):
+            raise ValueError("LateInteractionIndex.add: token shape or dtype differs from the stored ones")
+        if self._n and features.shape[1] != self._feat[0].shape[1]:
+            raise ValueError("LateInteractionIndex.add: embed dim differs from the stored one")
+        if ids is None:
+            ids = torch.arange(self._n, self._n + n, dtype=torch.int64)
+        else:
+            ids = torch.as_tensor(ids, dtype=torch.int64).reshape(-1)
+            if ids.numel() != n:
+                raise ValueError("LateInteractionIndex.add: one id per item")
+            self._running_ids = False
+        if self._chunk is None:
+            self._chunk = self._plan_chunk(tokens)
+        if self._n + n > self._ids.numel():
+            grown = torch.empty((max(2 * self._ids.numel(), self._n + n, 1024),), dtype=torch.int64, device=self.device)
+            grown[:self._n] = self._ids[:self._n]
+            self._ids = grown
+        self._ids[self._n:self._n + n] = ids.to(self.device)
+        done = 0
+        while done < n:
+            fill = self._n % self._chunk
+            want = min(self._chunk, fill + n - done)             # items of the last chunk after this round
+            have = self._feat[-1].shape[0] if fill else 0
+            if have < want:                                      # a new chunk, or the last one grows (doubling, up to a full chunk)
+                cap = min(self._chunk, max(want, 2 * have))
+                feat = torch.empty((cap, features.shape[1]), dtype=torch.float32, device=self.device)
+                tok = None if tokens is None else torch.empty((cap,) + tuple(tokens.shape[1:]), dtype=tokens.dtype, device=self.device)
+                if fill:
+                    feat[:fill] = self._feat.pop()[:fill]
+                    if tok is not None:
+                        tok[:fill] = self._tok.pop()[:fill]
+                self._feat.append(feat)
+                if tok is not None:
+                    self._tok.append(tok)
+            take = want - fill
+            self._feat[-1][fill:want] = features[done:done + take].detach().to(self.device)
+            if tokens is not None:
+                self._tok[-1][fill:want] = tokens[done:done + take].detach().to(self.device)
+            done += take
+            self._n += take
+        return self
+
+    def chunks(self):
+        """[(position of the first item, features [n, E], tokens [n, q, E] or None)] over the stored items"""
+        out = []
+        for c, feat in enumerate(self._feat):
+            base = c * self._chunk
+            n = min(self._chunk, self._n - base)
+            out.append((base, feat[:n], self._tok[c][:n] if self._tok else None))
+        return out
+
+    # ------------------------------------------------------------------ search
+    def search(self, features, tokens, k):
+        """features [nq, E] fp32 (normalised), tokens [nq, n, E] or None (alpha = 1) of the OTHER side -> (scores [nq, k] fp32,
+        ids [nq, k] int64) on the device, best first (larger score, then earlier gallery position); slots beyond the gallery
+        size hold (-inf, -1).  Nothing of size gallery x queries is allocated."""
+        nq = features.shape[0]
+        dev = self.device
+        if self.alpha == 1.0:
+            tokens = None
+        elif tokens is None or not self._tok and self._n:
+            raise ValueError("LateInteractionIndex.search: alpha != 1 needs token features on both sides")
+        features = features.detach().to(dev).float().contiguous()
+        best_val, best_idx = ops.topk_init(nq, k, dev)
+        if nq == 0 or self._n == 0:
+            return best_val, best_idx.to(torch.int64)
+        gallery_is_image = self.kind == "image"
+        qchunk = max(1, int(self.QUERY_CHUNK))
+        if not gallery_is_image and tokens is not None:
+            qchunk = image_chunk_items(qchunk, tokens.shape[1])
+        qchunk = min(qchunk, nq)
+        gchunk = min(self._chunk, self._n)
+        tile = torch.empty((gchunk, qchunk) if gallery_is_image else (qchunk, gchunk), dtype=torch.float32, device=dev)
+        s_dev = torch.tensor([self.scale], dtype=torch.float32, device=dev) if self.prescale else None
+        scale = 1.0 if self.prescale else self.scale
+        from .train import similarity_matrix
+        with torch.no_grad():
+            for q0 in range(0, nq, qchunk):
+                q1 = min(nq, q0 + qchunk)
+                qf = features[q0:q1]
+                qt = None if tokens is None else tokens[q0:q1].detach().to(dev)
+                for base, gf, gt in self.chunks():
+                    n = gf.shape[0]
+                    img_f, img_t, txt_f, txt_t = (gf, gt, qf, qt) if gallery_is_image else (qf, qt, gf, gt)
+                    view = tile[:n, :q1 - q0] if gallery_is_image else tile[:q1 - q0, :n]
+                    if s_dev is not None:
+                        img_f = ops.scale_by_dev(img_f.contiguous(), s_dev)
+                    G = similarity_matrix(img_f, txt_f)
+                    ops.maxsim_scores(img_t, txt_t, G, self.alpha, scale, out=view)
+                    ops.topk_merge(view, 1 if gallery_is_image else 0, base, best_val[q0:q1], best_idx[q0:q1])
+        pos = best_idx.to(torch.int64)
+        if self._running_ids:
+            return best_val, pos
+        found = self._ids[:self._n][pos.clamp_(min=0)]
+        return best_val, torch.where(best_idx >= 0, found, torch.full_like(found, -1))
+
+    # ------------------------------------------------------------------ through a model
+    @classmethod
+    def from_model(cls, model, kind, alpha=None, device=None):
+        """An empty index scored like `model`: a ColXLIP model gives alpha (default: the model's) and logit_scale.exp(); a plain
+        CLIP model scores on its global features alone (alpha = 1, the scale applied to the image features as in its
+        get_logits)."""
+        from .model import ColXLIP
+        from .train import unwrap_model
+        core = unwrap_model(model)
+        late = isinstance(core, ColXLIP)
+        if not late and alpha is not None and float(alpha) != 1.0:
+            raise ValueError("LateInteractionIndex.from_model: a model without token features scores with alpha = 1")
+        alpha = (core.alpha if alpha is None else float(alpha)) if late else 1.0
+        device = device or core.logit_scale.device
+        return cls(kind, alpha=alpha, scale=float(core.logit_scale.detach().exp()), device=device, prescale=not late)
+
+    @staticmethod
+    def _encode(model, what, batch):
+        from .train import unwrap_model
+        core = unwrap_model(model)
+        with torch.no_grad():
+            out = (core.encode_image if what == "image" else core.encode_text)(batch, normalize=True)
+        if isinstance(out, tuple):
+            return out[0].float(), out[1]
+        return out.float(), None
+
+    def _add_encoded(self, model, what, batch, ids):
+        if self.kind != what:
+            raise ValueError(f"LateInteractionIndex: this index holds {self.kind}s")
+        return self.add(*self._encode(model, what, batch), ids=ids)
+
+    def _search_encoded(self, model, what, batch, k):
+        if self.kind == what:
+            raise ValueError(f"LateInteractionIndex: an index of {self.kind}s is queried with the other side")
+        return self.search(*self._encode(model, what, batch), k)
+
+    def add_images(self, model, images, ids=None):
+        return self._add_encoded(model, "image", images, ids)
+
+    def add_texts(self, model, texts, ids=None):
+        return self._add_encoded(model, "text", texts, ids)
+
+    def search_texts(self, model, texts, k):
+        return self._search_encoded(model, "text", texts, k)
+
+    def search_images(self, model, images, k):
+        return self._search_encoded(model, "image", images, k)
+
+    # ------------------------------------------------------------------ files
+    def save(self, path):
+        """meta.json + features.npy [n, E] fp32 + tokens.npy [n, q, E] (bf16 as uint16 bit patterns; absent without tokens) +
+        ids.npy [n] int64, written chunk by chunk."""
+        os.makedirs(path, exist_ok=True)
+        e = self._feat[0].shape[1] if self._feat else 0
+        meta = {"kind": self.kind, "alpha": self.alpha, "scale": self.scale, "prescale": self.prescale, "n": self._n,
+                "embed_dim": e, "tokens": None, "token_dtype": None, "chunk_items": self._chunk}
+        feats = np.lib.format.open_memmap(os.path.join(path, "features.npy"), mode="w+", dtype=np.float32, shape=(self._n, e))
+        toks = None
+        if self._tok:
+            probe, name = _to_numpy(self._tok[0][:0])
+            meta["tokens"], meta["token_dtype"] = list(self._tok[0].shape[1:]), name
+            toks = np.lib.format.open_memmap(os.path.join(path, "tokens.npy"), mode="w+", dtype=probe.dtype,
+                                             shape=(self._n,) + tuple(self._tok[0].shape[1:]))
+        elif os.path.exists(os.path.join(path, "tokens.npy")):
+            os.remove(os.path.join(path, "tokens.npy"))
+        for base, gf, gt in self.chunks():
+            feats[base:base + gf.shape[0]] = gf.cpu().numpy()
+            if toks is not None:
+                toks[base:base + gf.shape[0]] = _to_numpy(gt)[0]
+        feats.flush()
+        if toks is not None:
+            toks.flush()
+        np.save(os.path.join(path, "ids.npy"), self.ids.cpu().numpy())
+        with open(os.path.join(path, "meta.json"), "w") as f:
+            json.dump(meta, f, indent=1)
+        return path
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        """The index `save` wrote: the arrays are memory-mapped and copied to `device` `IO_ITEMS` items at a time."""
+        with open(os.path.join(path, "meta.json")) as f:
+            meta = json.load(f)
+        index = cls(meta["kind"], alpha=meta["alpha"], scale=meta["scale"], device=device, prescale=meta.get("prescale", False))
+        n = int(meta["n"])
+        feats = np.load(os.path.join(path, "features.npy"), mmap_mode="r")
+        toks = np.load(os.path.join(path, "tokens.npy"), mmap_mode="r") if meta["tokens"] is not None else None
+        ids = np.load(os.path.join(path, "ids.npy"), mmap_mode="r")
+        if feats.shape[0] != n or ids.shape[0] != n or (toks is not None and toks.shape[0] != n):
+            raise ValueError(f"{path}: the arrays do not hold the {n} items meta.json names")
+        running = bool(n == 0 or np.array_equal(ids, np.arange(n, dtype=np.int64)))
+        step = max(1, int(cls.IO_ITEMS))
+        for lo in range(0, n, step):
+            hi = min(n, lo + step)
+            index.add(_from_numpy(feats[lo:hi], "float32"),
+                      None if toks is None else _from_numpy(toks[lo:hi], meta["token_dtype"]),
+                      ids=torch.from_numpy(np.array(ids[lo:hi])))
+        index._running_ids = running
+        return index
+
+
+# ---------------------------------------------------------------------------------------------------- command line
+def build_parser():
+    from .params import build_parser as train_parser
+    parser = train_parser()
+    parser.description = "index one side of a retrieval split and search it with the other"
+    parser.add_argument("--direction", choices=["t2i", "i2t"], default="t2i",
+                        help="t2i: text queries over the images; i2t: image queries over the captions")
+    parser.add_argument("--k", type=int, default=10)
+    parser.add_argument("--out", type=str, default=None, help="results.npz: scores, ids, query_ids")
+    parser.add_argument("--save-index", type=str, default=None)
+    parser.add_argument("--load-index", type=str, default=None)
+    return parser
+
+
+def parse_args(argv):
+    args = build_parser().parse_args(argv)
+    if args.save_index and args.load_index:
+        raise SystemExit("--save-index and --load-index exclude each other")
+    if not 1 <= args.k <= ops.TOPK_MAX_K:
+        raise SystemExit(f"--k must be in 1 .. {ops.TOPK_MAX_K}")
+    return args
+
+
+def recall_at(ids, query_ids, truth, ks=(1, 5, 10)):
+    """{K: share of queries with one of their true items among the first K returned ids}; `truth`: query id -> gallery id or
+    list of gallery ids.  Only K <= the number of returned columns."""
+    ids = np.asarray(ids)
+    hits = np.zeros(ids.shape, dtype=bool)
+    for row, qid in enumerate(np.asarray(query_ids).tolist()):
+        want = truth[int(qid)]
+        want = list(want) if isinstance(want, (list, tuple)) else [want]
+        hits[row] = np.isin(ids[row], np.asarray(want, dtype=np.int64))
+    return {K: float(hits[:, :K].any(axis=1).mean()) for K in ks if K <= ids.shape[1]}
+
+
+def run(args):
+    from .data import get_data
+    from .factory import create_model_and_transforms
+    from .model import ColXLIP, get_input_dtype
+    from .train import RETRIEVAL_SPLITS
+    args.rank, args.local_rank, args.world_size, args.distributed = 0, 0, 1, False
+    device = torch.device(args.device)
+    torch.manual_seed(args.seed)
+    model, pre_train, pre_val = create_model_and_transforms(
+        args.model, args.pretrained, precision=args.precision, device=device, force_quick_gelu=args.force_quick_gelu,
+        force_patch_dropout=args.force_patch_dropout, force_image_size=args.force_image_size, output_dict=True)
+    model.eval()
+    data = get_data(args, (pre_train, pre_val), model=model)
+    split = next((s for s in RETRIEVAL_SPLITS if s in data), None)
+    if split is None:
+        raise SystemExit("no retrieval split: pass --retrieval-coco or --retrieval-flickr")
+    txt_data, img_data, img2txt_dict, txt2img_dict = data[split]
+    input_dtype = get_input_dtype(args.precision)
+
+    def images():
+        for batch, ids in img_data.dataloader:
+            yield batch.to(device=device, dtype=input_dtype, non_blocking=True), torch.as_tensor(ids).reshape(-1).cpu()
+
+    def texts():
+        for batch, ids in txt_data.dataloader:
+            batch = batch.to(device=device, non_blocking=True)
+            yield (batch[:, 0] if batch.ndim == 3 else batch).contiguous(), torch.as_tensor(ids).reshape(-1).cpu()
+
+    t2i = args.direction == "t2i"
+    gallery, queries = (images, texts) if t2i else (texts, images)
+    kind, other = ("image", "text") if t2i else ("text", "image")
+    if args.load_index:
+        index = LateInteractionIndex.load(args.load_index, device)
+        if index.kind != kind:
+            raise SystemExit(f"{args.load_index} holds {index.kind}s; --direction {args.direction} needs {kind}s")
+    else:
+        alpha = None
+        if isinstance(model, ColXLIP):
+            alpha = 1.0 if getattr(args, "evaluate_as_original_clip", False) else float(args.alpha)
+        index = LateInteractionIndex.from_model(model, kind, alpha=alpha, device=device)
+        for batch, ids in gallery():
+            index._add_encoded(model, kind, batch, ids)
+        if args.save_index:
+            index.save(args.save_index)
+    scores, found, query_ids = [], [], []
+    for batch, ids in queries():
+        s, i = index._search_encoded(model, other, batch, args.k)
+        scores.append(s)
+        found.append(i)
+        query_ids.append(ids)
+    scores, found, query_ids = torch.cat(scores).cpu().numpy(), torch.cat(found).cpu().numpy(), torch.cat(query_ids).numpy()
+    truth = {int(c): [int(i) for i in (v if isinstance(v, (list, tuple)) else [v])] for c, v in
+             (txt2img_dict if t2i else img2txt_dict).items()}
+    name = "text_to_image" if t2i else "image_to_text"
+    metrics = {f"{name}_R@{K}": v for K, v in recall_at(found, query_ids, truth).items()}
+    logging.info(f"Search {split} {args.direction}: {len(query_ids)} queries over {len(index)} {kind}s, k = {args.k}\t" +
+                 "\t".join(f"{m}: {v:.4f}" for m, v in metrics.items()))
+    if args.out:
+        np.savez(args.out, scores=scores, ids=found, query_ids=query_ids,
+                 metric_names=np.array(list(metrics)), metric_values=np.array(list(metrics.values()), dtype=np.float64))
+    return metrics
+
+
+def main(argv=None):
+    import sys
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s | %(levelname)s | %(message)s")
+    run(parse_args(sys.argv[1:] if argv is None else argv))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

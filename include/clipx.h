@@ -408,6 +408,18 @@ int clipx_maxsim_scatter(int dtype, int ct, int n_tok, int groups, int q, const 
 int clipx_retrieval_rank(int rows, int cols, const float* scores, long ld, const int* tgt_off,
                          const int* tgt_idx, int* ranks, void* stream);
 
+/* ---- streaming top-k for late-interaction search (csrc/topk.hip; the reference ranks by sorting every row of the whole
+ * score matrix on the CPU, train.py:457-508) ------------------------------------------------------------------------
+ * One step of a running selection over a gallery that arrives tile by tile.  Tile: nq queries x nc candidates, fp32, element
+ * (j, c) at scores[j * q_stride + c * c_stride], exactly one of the strides 1 (both orientations of the image-major tile of
+ * clipx_maxsim_score_fold); candidate c is gallery position c_base + c.  best_val / best_idx [nq, k] (contiguous): afterwards a
+ * query's list holds the first k, under the total order "larger value, then smaller position", of its old list together with
+ * its candidates; values are copied bit for bit.  Empty slots are (-inf, -1) and sort last; -inf and NaN candidates are skipped.
+ * Refused before any launch: k outside 1 .. 256, both strides different from 1, c_base < 0 or c_base + nc > 2^31 - 1.
+ * nq == 0 or nc == 0 launches nothing.                                                                                   */
+int clipx_topk_merge(int nq, int nc, int k, const float* scores, long q_stride, long c_stride, long c_base, float* best_val,
+                     int* best_idx, void* stream);
+
 /* ---- kernel selection (tests / experiments; not part of the reference's interface) ---------------------------
  * bf16 NT GEMM structure: 0 = eight-wave kernel only, 1 = one-wave-per-SIMD kernel with the deferred epilogue wherever
  * it applies (full 256x256 tiles, bf16 output), 2 = that kernel only for tiles of >= 14 k-steps (the default), -1 = follow
