@@ -848,12 +848,14 @@ def clamp1(p, lo, hi):
 
 def cast_f32_bf16(x, out, scale=1.0):
     assert x.dtype == torch.float32 and out.dtype == torch.bfloat16 and x.numel() == out.numel()
+    assert out.is_contiguous(), "cast_f32_bf16 writes through out's pointer: out must be contiguous"
     check(_lib.lib().clipx_cast_f32_bf16(x.numel(), _p(_c(x)), _p(_c(out)), float(scale), _stream()))
     return out
 
 
 def cast_bf16_f32(x, out, scale=1.0):
     assert x.dtype == torch.bfloat16 and out.dtype == torch.float32 and x.numel() == out.numel()
+    assert out.is_contiguous(), "cast_bf16_f32 writes through out's pointer: out must be contiguous"
     check(_lib.lib().clipx_cast_bf16_f32(x.numel(), _p(_c(x)), _p(_c(out)), float(scale), _stream()))
     return out
 
