@@ -414,6 +414,27 @@ extern "C" int clipx_maxsim_gemm(int R, int ni, int q, int e, const void* packed
     return 0;
 }
 
+// the same partials from e4m3 operands on the fp8 MFMA (gemm_fp8_nt8p.hip): packed8 [R, e] / img8 [ni * q, e] bytes with one
+// power-of-two exponent per row (clipx_quant_rows_e4m3).  A shape the kernel does not take is an error: the caller chooses the
+// route before it calls.
+extern "C" int clipx_maxsim_gemm_fp8(int R, int ni, int q, int e, const void* packed8, const int* packed_exp, const void* img8,
+                                     const int* img_exp, float* pmax, unsigned short* pidx, int ld, void* stream) {
+    CLIPX_CHECK(q >= 16 && q <= 65535 && e % 128 == 0 && e >= 256 && ld >= R,
+                "maxsim_gemm_fp8: needs q >= 16, embed dim %% 128 == 0 and >= 256 (q=%d e=%d)", q, e);
+    if (R <= 0 || ni <= 0) return 0;
+    CLIPX_CHECK(packed8 && packed_exp && img8 && img_exp && pmax && pidx, "maxsim_gemm_fp8: null operand");
+    EpiB16 epi = {};
+    epi.ms_max = pmax;
+    epi.ms_idx = pidx;
+    epi.ms_q = q;
+    epi.ms_ld = ld;
+    const int rc = launch_gemm_fp8_nt8p_maxsim(R, ni * q, e, (const unsigned char*)packed8, packed_exp, (const unsigned char*)img8,
+                                               img_exp, epi, (hipStream_t)stream);
+    CLIPX_CHECK(rc == 0, "maxsim_gemm_fp8: the fp8 ping-pong NT kernel does not take this shape or alignment (R=%d ni*q=%d e=%d)", R,
+                ni * q, e);
+    return 0;
+}
+
 extern "C" int clipx_maxsim_finish(int R, int ldp, int r0, int ld, int ni, int q, const float* pmax, const unsigned short* pidx,
                                    float* maxvT, unsigned short* argT, void* stream) {
     if (R <= 0 || ni <= 0) return 0;

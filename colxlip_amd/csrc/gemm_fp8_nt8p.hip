@@ -8,8 +8,14 @@
 // rings and LDS-DMA pieces; a lane's MFMA operand is 32 consecutive k of one row = the two 16-byte chunks 2g, 2g+1 of the row (two
 // ds_read_b128 into one 8-VGPR tuple), so a C segment is 32 MFMAs of 32 cycles: the same 1024 cycles as 64 bf16 MFMAs, for
 // twice the K; and the row exponents are applied to the accumulators before the tile epilogue.
+//
+// The MaxSim instances (F_MAXSIM, F_MAXSIM_SEG) end a tile in the reductions of gemm_nt_maxsim.h instead: x8 = packed text rows,
+// w8 = image tokens.  The column exponent we[n] differs per image token and therefore decides which token wins, so it has to be
+// on the accumulators BEFORE the maximum; the row exponent is a positive factor and could follow it, but one scaling loop
+// serves both.  The partial arrays are those of the bf16 instances, value for value in layout and tie rules.
 #include "gemm_nt_pp.h"
 #include "gemm_nt_epilogue.h"
+#include "gemm_nt_maxsim.h"
 
 typedef __attribute__((ext_vector_type(4))) int f8x16;      // 16 fp8 bytes
 typedef __attribute__((ext_vector_type(8))) int f8x32;      // one lane's MFMA operand: 32 fp8 bytes
@@ -52,6 +58,37 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_nt8p_kernel(int M, int N, int
         // the row exponents: acc[n-tile i][m-tile j][q] belongs to row 16j + c, column 16i + 4g + q of the wave's 128 x 64
         const int g = lane >> 4, c = lane & 15;
         const int m_base = m0 + wm * 128 + c, n_base = n0 + wn * 64 + 4 * g;
+        if constexpr ((FL & F_MAXSIM) != 0) {
+            // the same factors in two passes, columns then rows, read through buffer descriptors: one 32-bit offset per operand
+            // instead of twelve 64-bit addresses beside the 128 accumulators (the form below spilled two VGPRs here), and an index
+            // past the end reads exponent 0 without a clamp.  Powers of two, so the order of the factors changes no value.
+            const __amdgpu_buffer_rsrc_t re = __builtin_amdgcn_make_buffer_rsrc((void*)sc.xe, 0, M * 4, 0x00020000);
+            const __amdgpu_buffer_rsrc_t ce = __builtin_amdgcn_make_buffer_rsrc((void*)sc.we, 0, N * 4, 0x00020000);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float sq[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    sq[q] = __builtin_ldexpf(1.0f, __builtin_amdgcn_raw_buffer_load_b32(ce, 4 * n_base + 4 * (16 * i + q), 0, 0));
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) acc[i][j][q] *= sq[q];
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float sr = __builtin_ldexpf(1.0f, __builtin_amdgcn_raw_buffer_load_b32(re, 4 * m_base + 64 * j, 0, 0));
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) acc[i][j][q] *= sr;
+            }
+            if constexpr ((FL & F_MAXSIM_SEG) != 0)
+                nt_maxsim_seg_epilogue<8>(acc, epi, M, N, m0, n0, wm, wn, lane);
+            else
+                nt_maxsim_epilogue<8>(acc, epi, M, N, m0, n0, wm, wn, lane);
+            return;
+        }
         float sr[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) sr[j] = __builtin_ldexpf(1.0f, sc.xe[min(m_base + 16 * j, M - 1)]);
@@ -69,6 +106,21 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_nt8p_kernel(int M, int N, int
     });
 }
 
+// S = 2^(xe[m] + we[n]) * X8 . W8^T reduced on the fly to the MaxSim partials (gemm_nt_maxsim.h), as
+// launch_gemm_bf16_nt8p_maxsim does for bf16 operands; nothing else is written.  1 = this kernel does not apply.
+int launch_gemm_fp8_nt8p_maxsim(int M, int N, int K, const unsigned char* X, const int* xe, const unsigned char* W, const int* we,
+                                const EpiB16& epi, hipStream_t stream) {
+    if (K % 128 != 0 || K < 256 || (long)256 * K >= (1l << 31) || epi.ms_q < 16 || epi.ms_q > 65535 || N % 8 != 0) return 1;
+    if (((uintptr_t)X % 16 != 0) || ((uintptr_t)W % 16 != 0)) return 1;
+    if (M <= 0 || N <= 0) return 0;
+    const F8Scales sc{xe, we};
+    if (epi.ms_q < 64)
+        return pp_launch<gemm_fp8_nt8p_kernel<bf16_t, F_MAXSIM | F_MAXSIM_SEG, CLIPX_ACT_NONE>>(
+            M, N, K, X, W, epi, (bf16_t*)nullptr, clipx_num_cu(false), stream, sc);
+    return pp_launch<gemm_fp8_nt8p_kernel<bf16_t, F_MAXSIM, CLIPX_ACT_NONE>>(M, N, K, X, W, epi, (bf16_t*)nullptr,
+                                                                             clipx_num_cu(false), stream, sc);
+}
+
 // y = epi(x8 . w8^T) for e4m3 operands with per-row exponents; bf16 output.  Needs K % 128 == 0.
 int launch_gemm_fp8_nt(int M, int N, int K, const unsigned char* X, const int* xe, const unsigned char* W, const int* we,
                        const EpiB16& epi, bf16_t* out, hipStream_t stream) {
@@ -81,7 +133,7 @@ int launch_gemm_fp8_nt(int M, int N, int K, const unsigned char* X, const int* x
     const F8Scales sc{xe, we};
     int fl, act;
     CLIPX_CHECK(nt_epi_flags(epi, fl, act), "fp8 NT GEMM: act and act_u are mutually exclusive");
-    CLIPX_CHECK(!epi.ms_max, "fp8 NT GEMM: the MaxSim epilogue is built for the bf16 kernel only");
+    CLIPX_CHECK(!epi.ms_max, "fp8 NT GEMM: the MaxSim epilogue has its own launch (launch_gemm_fp8_nt8p_maxsim)");
 #define F8_CASE(FLV, ACTV)             \
     if (fl == (FLV) && act == (ACTV)) \
     return pp_launch<gemm_fp8_nt8p_kernel<bf16_t, (FLV), (ACTV)>>(M, N, K, X, W, epi, out, n_cu, stream, sc)

@@ -39,6 +39,8 @@ int launch_gemm_bf16_nt8p(int M, int N, int K, const bf16_t* X, const bf16_t* W,
 int launch_gemm_bf16_nt8p_maxsim(int M, int N, int K, const bf16_t* X, const bf16_t* W, const EpiB16& epi, hipStream_t stream);
 int launch_gemm_fp8_nt(int M, int N, int K, const unsigned char* X, const int* xe, const unsigned char* W, const int* we,
                        const EpiB16& epi, bf16_t* out, hipStream_t stream);
+int launch_gemm_fp8_nt8p_maxsim(int M, int N, int K, const unsigned char* X, const int* xe, const unsigned char* W, const int* we,
+                                const EpiB16& epi, hipStream_t stream);   // 1 = does not apply
 int launch_gemm_bf16_tn(int M, int N, int K, const bf16_t* DY, const bf16_t* X, float* dw, float beta, float* db,
                         float beta_b, void* ws, size_t ws_bytes, hipStream_t stream);
 size_t gemm_bf16_tn_ws_bytes(int M, int N, int K);

@@ -76,6 +76,26 @@ def quant_rows_e4m3(x):
     return x8, xe
 
 
+def quant_tokens_e4m3(tokens):
+    """tokens [n, q, E] bf16 -> (bytes [n, q, E] uint8 of e4m3, exp [n, q] int32): `quant_rows_e4m3` on the n * q token rows, one
+    power-of-two exponent per token.  The stored form of a late-interaction index (search.py) and the operand form of
+    `maxsim_scores_fp8`."""
+    n, q, e = tokens.shape
+    assert tokens.dtype == torch.bfloat16
+    if n * q == 0:
+        return (torch.empty((n, q, e), dtype=torch.uint8, device=tokens.device),
+                torch.empty((n, q), dtype=torch.int32, device=tokens.device))
+    x8, xe = quant_rows_e4m3(tokens.contiguous().view(n * q, e))
+    return x8.view(n, q, e), xe.view(n, q)
+
+
+def dequant_tokens_e4m3(x8, exp, dtype=torch.float32):
+    """(bytes [..., E] uint8, exp [...] int32) -> bytes read as float8_e4m3fn times 2^exp, in `dtype`; plain torch, CPU tensors too.
+    Every value is exact in fp32 and in bf16 (three mantissa bits)."""
+    assert x8.dtype == torch.uint8 and x8.shape[:-1] == exp.shape
+    return torch.ldexp(x8.view(torch.float8_e4m3fn).to(torch.float32), exp.unsqueeze(-1).to(torch.int32)).to(dtype)
+
+
 @family("gemm_nt.fwd_fp8")
 def linear_fwd_fp8(x8, xe, w8, we, bias=None, act=ACT_NONE, want_preact=False, residual=None, out=None):
     """y (bf16) = act(2^(xe[m] + we[n]) * x8 @ w8.T + bias) (+ residual) on the fp8 MFMA.  x8 [M,K], w8 [N,K] uint8 (e4m3)."""
@@ -903,6 +923,17 @@ def maxsim_pack_text(txt):
     return cu, int(cu[nt].item())
 
 
+def maxsim_text_counts(txt):
+    """txt [nt, n, e] bf16 -> cnt int32 [nt]: the packed rows per sample as `maxsim_pack_text` counts them (leading rows + one
+    representative of the bitwise-equal tail), without the read-back."""
+    nt, n, e = txt.shape
+    cnt = torch.empty((nt,), dtype=torch.int32, device=txt.device)
+    cu = torch.empty((nt + 1,), dtype=torch.int32, device=txt.device)
+    if nt:
+        check(_lib.lib().clipx_maxsim_pack_text(nt, n, e, _p(_c(txt)), _p(cnt), _p(cu), _stream()))
+    return cnt
+
+
 def maxsim_pack_rows(txt, cu, R):
     nt, n, e = txt.shape
     packed = torch.empty((R, e), dtype=txt.dtype, device=txt.device)
@@ -915,6 +946,16 @@ def maxsim_pack_rows(txt, cu, R):
 def maxsim_gemm(packed, img, ni, q, pmax, pidx, ldp):
     R, e = packed.shape
     check(_lib.lib().clipx_maxsim_gemm(R, ni, q, e, _p(_c(packed)), _p(_c(img)), _p(pmax), _p(pidx), ldp, _nt_stream()))
+
+
+@family("gemm_nt.fwd_fp8")
+def maxsim_gemm_fp8(packed8, packed_exp, img8, img_exp, ni, q, pmax, pidx, ldp):
+    """the partials of `maxsim_gemm` from e4m3 rows with per-row exponents, on the fp8 MFMA"""
+    R, e = packed8.shape
+    assert packed8.dtype == torch.uint8 and img8.dtype == torch.uint8 and img8.shape == (ni * q, e)
+    assert packed_exp.dtype == torch.int32 and packed_exp.numel() == R and img_exp.dtype == torch.int32 and img_exp.numel() == ni * q
+    check(_lib.lib().clipx_maxsim_gemm_fp8(R, ni, q, e, _p(_c(packed8)), _p(_c(packed_exp)), _p(_c(img8)), _p(_c(img_exp)), _p(pmax),
+                                           _p(pidx), ldp, _nt_stream()))
 
 
 def maxsim_finish(R, ldp, r0, ld, ni, q, pmax, pidx, maxvT, argT):
@@ -980,11 +1021,11 @@ def maxsim_partial_bytes(ci: int, q: int, rows: int) -> int:
     return 6 * maxsim_partial_rows(ci, q) * maxsim_partial_ld(rows)
 
 
-def plan_maxsim_chunks(ni, q, e, cu_host, partial_bytes, operand_bytes=None):
+def plan_maxsim_chunks(ni, q, e, cu_host, partial_bytes, operand_bytes=None, elem_bytes=2):
     """Chunk plan of `maxsim_scores` on the fused route; pure Python.  Returns (image_chunks, text_chunks):
       image_chunks [(k0, k1, ci)]: images k0 .. k1 go through the GEMM as `ci >= k1 - k0` images, the last ci - (k1 - k0) of
-        them zero padding, with (ci * q) % 8 == 0 (GEMM alignment), ci <= 65535 and ci * q * e bf16 elements below
-        `operand_bytes`; only the last chunk can need padding;
+        them zero padding, with (ci * q) % 8 == 0 (GEMM alignment), ci <= 65535 and ci * q * e elements of `elem_bytes` bytes
+        (2: bf16, 1: e4m3) below `operand_bytes`; only the last chunk can need padding;
       text_chunks [(m0, m1, r0, r1)]: runs of whole samples (packed rows cu[m0] = r0 .. cu[m1] = r1) whose partial arrays
         against the largest image chunk stay within `partial_bytes`; a single sample that does not fit is a chunk of its own.
     The image chunk is as large as the operand limit allows, but no larger than lets MAXSIM_TARGET_ROWS packed rows (or all of
@@ -996,7 +1037,7 @@ def plan_maxsim_chunks(ni, q, e, cu_host, partial_bytes, operand_bytes=None):
     unit = 8 // math.gcd(q, 8)                                   # image counts with (ci * q) % 8 == 0
     want_ld = maxsim_partial_ld(max(1, min(MAXSIM_TARGET_ROWS, cu_host[nt])))
     fit = partial_bytes // (12 * want_ld)                        # slots (q >= 64) or images whose partials fit
-    cmax = min(MAXSIM_MAX_IMAGES, operand_bytes // (2 * q * e), fit if q < 64 else fit * 64 // q)
+    cmax = min(MAXSIM_MAX_IMAGES, operand_bytes // (int(elem_bytes) * q * e), fit if q < 64 else fit * 64 // q)
     cmax = max(unit, cmax // unit * unit)
     cmax = min(cmax, (ni + unit - 1) // unit * unit)
     image_chunks = []
@@ -1121,6 +1162,108 @@ def maxsim_scores(tok_img, tok_txt, G, alpha, scale, out=None):
         if maxsim_fused_applies(tok_img, tok_txt):
             return _maxsim_scores_fused(tok_img.detach(), tok_txt.detach(), G, alpha, scale, out)
         return _maxsim_scores_general(tok_img.detach(), tok_txt.detach(), G, alpha, scale, out)
+
+
+# ------------------------------------------------------------------ late-interaction scoring on e4m3 tokens
+# Either side of `maxsim_scores_fp8` is a bf16 tensor (quantised on the fly) or its stored form: an image side (bytes [ni, q, e]
+# uint8, exp [ni, q] int32), a text side (bytes [nt, n, e], exp [nt, n], cnt [nt] int32) with cnt = `maxsim_text_counts` of the
+# bf16 rows.  The quantiser works row by row, so the packed rows of a stored text side are the rows the on-the-fly route
+# quantises after packing, byte for byte.
+def _fp8_side(x):
+    """(tensor that carries shape [items, tokens, e] and device, stored?)"""
+    if isinstance(x, (tuple, list)):
+        return x[0], True
+    return x, False
+
+
+def maxsim_fp8_applies(img, txt) -> bool:
+    """whether `maxsim_scores_fp8` runs the fp8 MaxSim GEMM on these sides (else: the general fp32 route on dequantised values)"""
+    ti, si = _fp8_side(img)
+    tt, st = _fp8_side(txt)
+    ni, q, e = ti.shape
+    ok_i = ti.dtype == (torch.uint8 if si else torch.bfloat16)
+    ok_t = tt.dtype == (torch.uint8 if st else torch.bfloat16)
+    return (ok_i and ok_t and ti.is_cuda and tt.is_cuda and 16 <= q <= 65535 and e % 128 == 0 and e >= 256
+            and os.environ.get("CLIPX_MAXSIM_FUSED", "1") != "0")
+
+
+def _fp8_pack_stored_text(t8, te, cnt):
+    """stored text side -> (packed8 [R, e], packed_exp [R], cu [nt + 1] int32, row_w [R]): the rows `maxsim_pack_rows` picks"""
+    nt, n, e = t8.shape
+    cu = torch.zeros((nt + 1,), dtype=torch.int32, device=t8.device)
+    cu[1:] = torch.cumsum(cnt, 0)
+    R = int(cu[nt].item())
+    packed, row_m, row_w = maxsim_pack_rows(t8.contiguous().view(torch.bfloat16), cu, R)        # a byte row as e / 2 bf16: a copy
+    pos = torch.arange(R, dtype=torch.int64, device=t8.device) - cu[:-1].long()[row_m.long()]
+    return packed.view(torch.uint8), te.contiguous().view(-1)[row_m.long() * n + pos].contiguous(), cu, row_w
+
+
+def _maxsim_scores_fp8_fused(img, txt, G, alpha, scale, out):
+    from .loss import _MaxSimFused
+    ti, stored_i = _fp8_side(img)
+    ni, q, e = ti.shape
+    dev = ti.device
+    i8, ie = (img[0], img[1]) if stored_i else quant_tokens_e4m3(img)
+    i8, ie = i8.contiguous().view(ni * q, e), ie.contiguous().view(ni * q)
+    if isinstance(txt, (tuple, list)):
+        p8, pe, cu, row_w = _fp8_pack_stored_text(*txt)
+    else:
+        t = txt.contiguous()
+        cu, R = maxsim_pack_text(t)
+        packed, _, row_w = maxsim_pack_rows(t, cu, R)
+        p8, pe = quant_rows_e4m3(packed)
+    image_chunks, text_chunks = plan_maxsim_chunks(ni, q, e, cu.cpu().tolist(), _MaxSimFused.CHUNK_BYTES, elem_bytes=1)
+    cmax = max(c for _, _, c in image_chunks)
+    ldmax = maxsim_partial_ld(max(r1 - r0 for _, _, r0, r1 in text_chunks))
+    prow = maxsim_partial_rows(cmax, q)
+    pmax = torch.empty((prow * ldmax,), dtype=torch.float32, device=dev)
+    pidx = torch.empty((prow * ldmax,), dtype=torch.int16, device=dev)
+    for k0, k1, ci in image_chunks:
+        if ci == k1 - k0:
+            op8, ope = i8[k0 * q:k1 * q], ie[k0 * q:k1 * q]
+        else:                                                   # zero images (byte 0, exponent 0) behind the last ones: never folded
+            op8 = torch.zeros((ci * q, e), dtype=torch.uint8, device=dev)
+            ope = torch.zeros((ci * q,), dtype=torch.int32, device=dev)
+            op8[:(k1 - k0) * q] = i8[k0 * q:k1 * q]
+            ope[:(k1 - k0) * q] = ie[k0 * q:k1 * q]
+        for m0, m1, r0, r1 in text_chunks:
+            ldp = maxsim_partial_ld(r1 - r0)
+            maxsim_gemm_fp8(p8[r0:r1], pe[r0:r1], op8, ope, ci, q, pmax, pidx, ldp)
+            maxsim_score_fold(m1 - m0, k1 - k0, q, ldp, r0, cu, m0, row_w, pmax, None if G is None else G[k0:k1, m0:m1],
+                              out[k0:k1, m0:m1], alpha, scale)
+    return out
+
+
+def maxsim_scores_fp8(img, txt, G, alpha, scale, out=None):
+    """`maxsim_scores` on e4m3 token features: the same contract and output, scores [ni, nt] fp32 image-major =
+        scale * (alpha * G + (1 - alpha) * MaxSim(dequantised img, dequantised txt)^T).
+    Each side is a bf16 tensor (quantised here, per token row) or its stored form, (bytes, exp) for images and (bytes, exp, cnt)
+    for texts (see above).  With 16 <= q, e % 128 == 0 and e >= 256 on the device the MaxSim GEMM runs on the fp8 MFMA
+    (`clipx_maxsim_gemm_fp8`; products exact, sums fp32, both exponents applied before the maximum) and
+    `clipx_maxsim_score_fold` finishes as on the bf16 route.  Otherwise (`maxsim_fp8_applies` is False) the quantised
+    operands are dequantised to fp32 and scored by the general route: the same numbers up to summation order.  alpha = 1 is
+    scale * G bit for bit; no token kernel runs and the token sides are not looked at."""
+    alpha, scale = float(alpha), float(scale)
+    if alpha == 1.0:
+        return maxsim_scores(None, None, G, 1.0, scale, out=out)
+    ti, stored_i = _fp8_side(img)
+    tt, stored_t = _fp8_side(txt)
+    ni, q, e = ti.shape
+    nt, n, e2 = tt.shape
+    assert e == e2 and ti.device == tt.device
+    if G is not None:
+        assert G.shape == (ni, nt) and G.dtype == torch.float32
+        if G.stride(1) != 1:
+            G = G.contiguous()
+    if out is None:
+        out = torch.empty((ni, nt), dtype=torch.float32, device=ti.device)
+    assert out.shape == (ni, nt) and out.dtype == torch.float32 and out.stride(1) == 1
+    with torch.no_grad():
+        if maxsim_fp8_applies(img, txt):
+            return _maxsim_scores_fp8_fused(img, txt, G, alpha, scale, out)
+        i8, ie = (img[0], img[1]) if stored_i else quant_tokens_e4m3(img.detach())
+        t8, te = (txt[0], txt[1]) if stored_t else quant_tokens_e4m3(txt.detach())
+        return _maxsim_scores_general(dequant_tokens_e4m3(i8, ie), dequant_tokens_e4m3(t8, te), G, alpha, scale, out)
 
 
 # ------------------------------------------------------------------ streaming top-k (late-interaction search)

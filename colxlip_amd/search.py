@@ -8,6 +8,10 @@ arithmetic); the selection replaces the reference's per-row CPU argsort (train.p
 
     python -m colxlip_amd.search --model NAME [--pretrained CKPT] [--precision bf16] --dataset-type synthetic|packed
         [--val-data DIR] --retrieval-coco --direction t2i|i2t --k 10 --out results.npz [--save-index DIR | --load-index DIR]
+        [--index-dtype model|fp8]
+
+`token_dtype="fp8"` keeps the gallery's token features as e4m3 bytes with one power-of-two exponent per token
+(`ops.quant_tokens_e4m3`): half the bytes of bf16 plus 4 per token, scored by `ops.maxsim_scores_fp8` on the fp8 MFMA.
 """
 import json
 import logging
@@ -20,6 +24,7 @@ import torch
 from . import ops
 
 _FILES = ("meta.json", "features.npy", "tokens.npy", "ids.npy")
+_FP8_FILES = ("token_exp.npy", "token_cnt.npy")     # beside tokens.npy (uint8) of an fp8 index; token_cnt.npy: text galleries only
 
 
 def topk_reference(scores, k, query_dim, c_base=0, best=None):
@@ -77,20 +82,28 @@ class LateInteractionIndex:
         scale * (alpha * global + (1 - alpha) * MaxSim(tokens))
     as `ops.maxsim_scores` computes it.  `prescale` moves the scale onto the image features BEFORE the similarity GEMM,
     (scale * I) T^T, which is how a plain CLIP model forms its logits (reference train.py:608); it needs alpha = 1.
-    A model's logit_bias is not part of the scores: a constant does not change a ranking."""
+    A model's logit_bias is not part of the scores: a constant does not change a ranking.
+
+    `token_dtype=None` stores the tokens as they come; `token_dtype="fp8"` stores e4m3 bytes [chunk, q, E] uint8 with exponents
+    [chunk, q] int32 (`ops.quant_tokens_e4m3`), for a text gallery also cnt [chunk] int32 (`ops.maxsim_text_counts` of the bf16
+    rows), and scores both directions with `ops.maxsim_scores_fp8`: MaxSim of the dequantised tokens."""
 
     CHUNK_ITEMS = 16384          # gallery items per chunk (storage and scoring)
     QUERY_CHUNK = 8192           # queries per chunk: the score tile is at most CHUNK_ITEMS x QUERY_CHUNK x 4 bytes
     IO_ITEMS = 65536             # items per copy of save / load
 
-    def __init__(self, kind="image", alpha=0.5, scale=1.0, device="cuda", prescale=False):
+    def __init__(self, kind="image", alpha=0.5, scale=1.0, device="cuda", prescale=False, token_dtype=None):
         if kind not in ("image", "text"):
             raise ValueError(f"LateInteractionIndex: kind must be 'image' or 'text' (got {kind!r})")
+        if token_dtype not in (None, "fp8"):
+            raise ValueError(f"LateInteractionIndex: token_dtype must be None (the model's dtype) or 'fp8' (got {token_dtype!r})")
+        self.token_dtype = token_dtype
         if prescale and float(alpha) != 1.0:
             raise ValueError("LateInteractionIndex: prescale is the plain CLIP form of the logits and needs alpha = 1")
         self.kind, self.alpha, self.scale, self.prescale = kind, float(alpha), float(scale), bool(prescale)
         self.device = torch.device(device)
         self._feat, self._tok = [], []           # chunks [chunk, E] fp32 / [chunk, q, E]; the last one may be partly filled
+        self._tok_exp, self._tok_cnt = [], []    # fp8: chunks [chunk, q] int32 / (text gallery) [chunk] int32 beside the bytes in _tok
         self._ids = torch.empty((0,), dtype=torch.int64, device=self.device)      # capacity doubles
         self._n = 0
         self._chunk = None                       # items per chunk, fixed by the first add
@@ -116,7 +129,10 @@ class LateInteractionIndex:
     def add(self, features, tokens=None, ids=None):
         """features [n, E] fp32, normalised; tokens [n, q, E] in the model's compute dtype (None: a model without token features,
         alpha must be 1); ids int64 [n] (default: the running position).  Storage grows by chunks of `CHUNK_ITEMS` items; only the
-        last, partly filled chunk is ever copied (it doubles up to a full chunk)."""
+        last, partly filled chunk is ever copied (it doubles up to a full chunk).
+        An fp8 index takes the same bf16 tokens and quantises them as they arrive; fp32 tokens are cast to bf16 first, which
+        ROUNDS them (8 significant bits) before the e4m3 step.  It also takes the stored form itself, (bytes, exp) or for a text
+        gallery (bytes, exp, cnt), as `chunks` yields it: that is kept byte for byte (`load` uses it)."""
         n = features.shape[0]
         if features.dim() != 2 or features.dtype != torch.float32:
             raise ValueError("LateInteractionIndex.add: features must be [n, E] fp32")
@@ -124,6 +140,9 @@ class LateInteractionIndex:
             tokens = None                        # never read
         elif tokens is None:
             raise ValueError("LateInteractionIndex.add: alpha != 1 scores with token features; pass tokens or use alpha = 1")
+        extra = ()                               # fp8: (exp [n, q],) or (exp, cnt [n]) beside the bytes
+        if tokens is not None and self.token_dtype == "fp8":
+            tokens, *extra = self._quantise(tokens, n)
         if tokens is not None and (tokens.dim() != 3 or tokens.shape[0] != n or tokens.shape[2] != features.shape[1]):
             raise ValueError("LateInteractionIndex.add: tokens must be [n, q, E] with the features' n and E")
         if self._n and tokens is not None and (tokens.shape[1:] != self._tok[0].shape[1:] or tokens.dtype != self._tok[0].dtype):
@@ -153,35 +172,71 @@ class LateInteractionIndex:
                 cap = min(self._chunk, max(want, 2 * have))
                 feat = torch.empty((cap, features.shape[1]), dtype=torch.float32, device=self.device)
                 tok = None if tokens is None else torch.empty((cap,) + tuple(tokens.shape[1:]), dtype=tokens.dtype, device=self.device)
+                side = [torch.empty((cap,) + tuple(x.shape[1:]), dtype=torch.int32, device=self.device) for x in extra]
                 if fill:
                     feat[:fill] = self._feat.pop()[:fill]
                     if tok is not None:
                         tok[:fill] = self._tok.pop()[:fill]
+                    for new, store in zip(side, (self._tok_exp, self._tok_cnt)):
+                        new[:fill] = store.pop()[:fill]
                 self._feat.append(feat)
                 if tok is not None:
                     self._tok.append(tok)
+                for new, store in zip(side, (self._tok_exp, self._tok_cnt)):
+                    store.append(new)
             take = want - fill
             self._feat[-1][fill:want] = features[done:done + take].detach().to(self.device)
             if tokens is not None:
                 self._tok[-1][fill:want] = tokens[done:done + take].detach().to(self.device)
+            for x, store in zip(extra, (self._tok_exp, self._tok_cnt)):
+                store[-1][fill:want] = x[done:done + take].to(self.device)
             done += take
             self._n += take
         return self
 
+    def _quantise(self, tokens, n):
+        """tokens of an fp8 index -> (bytes [n, q, E] uint8, exp [n, q] int32[, cnt [n] int32 for a text gallery]) on the device"""
+        want = 3 if self.kind == "text" else 2
+        if isinstance(tokens, (tuple, list)):                    # the stored form, kept as it is
+            if len(tokens) != want or tokens[0].dtype != torch.uint8 or any(x.dtype != torch.int32 for x in tokens[1:]):
+                raise ValueError(f"LateInteractionIndex.add: the stored form of {self.kind} tokens is "
+                                 f"(bytes uint8, exp int32{', cnt int32' if want == 3 else ''})")
+            if tokens[0].dim() != 3 or tokens[1].shape != tokens[0].shape[:2] or (want == 3 and tokens[2].shape != tokens[0].shape[:1]):
+                raise ValueError("LateInteractionIndex.add: bytes [n, q, E], exp [n, q] and cnt [n] must agree")
+            return tuple(x.detach().to(self.device) for x in tokens)
+        if tokens.dtype not in (torch.bfloat16, torch.float32):
+            raise ValueError("LateInteractionIndex.add: token dtype differs from the stored ones: an fp8 index takes bf16 tokens "
+                             "(or fp32, rounded to bf16)")
+        if tokens.dim() != 3 or tokens.shape[0] != n:
+            raise ValueError("LateInteractionIndex.add: tokens must be [n, q, E] with the features' n and E")
+        tokens = tokens.detach().to(self.device).to(torch.bfloat16).contiguous()
+        out = ops.quant_tokens_e4m3(tokens)
+        return out + (ops.maxsim_text_counts(tokens),) if want == 3 else out
+
     def chunks(self):
-        """[(position of the first item, features [n, E], tokens [n, q, E] or None)] over the stored items"""
+        """[(position of the first item, features [n, E], tokens [n, q, E] or None)] over the stored items; an fp8 index yields
+        its stored form in the place of the tokens: (bytes [n, q, E], exp [n, q]), for a text gallery (bytes, exp, cnt [n])"""
         out = []
         for c, feat in enumerate(self._feat):
             base = c * self._chunk
             n = min(self._chunk, self._n - base)
-            out.append((base, feat[:n], self._tok[c][:n] if self._tok else None))
+            tok = self._tok[c][:n] if self._tok else None
+            if tok is not None and self.token_dtype == "fp8":
+                tok = (tok, self._tok_exp[c][:n]) + ((self._tok_cnt[c][:n],) if self.kind == "text" else ())
+            out.append((base, feat[:n], tok))
         return out
+
+    def token_bytes(self):
+        """bytes of the stored token tensors (an fp8 index: bytes, exponents and counts), whole chunks as allocated"""
+        return sum(t.numel() * t.element_size() for store in (self._tok, self._tok_exp, self._tok_cnt) for t in store)
 
     # ------------------------------------------------------------------ search
     def search(self, features, tokens, k):
         """features [nq, E] fp32 (normalised), tokens [nq, n, E] or None (alpha = 1) of the OTHER side -> (scores [nq, k] fp32,
         ids [nq, k] int64) on the device, best first (larger score, then earlier gallery position); slots beyond the gallery
-        size hold (-inf, -1).  Nothing of size gallery x queries is allocated."""
+        size hold (-inf, -1).  Nothing of size gallery x queries is allocated.  An fp8 index quantises the query tokens once per
+        query chunk (fp32 ones are cast to bf16 first) and scores with `ops.maxsim_scores_fp8`; no bf16 copy of a gallery chunk
+        is made."""
         nq = features.shape[0]
         dev = self.device
         if self.alpha == 1.0:
@@ -207,6 +262,9 @@ class LateInteractionIndex:
                 q1 = min(nq, q0 + qchunk)
                 qf = features[q0:q1]
                 qt = None if tokens is None else tokens[q0:q1].detach().to(dev)
+                if qt is not None and self.token_dtype == "fp8":
+                    qt = qt.to(torch.bfloat16).contiguous()
+                    qt = ops.quant_tokens_e4m3(qt) + ((ops.maxsim_text_counts(qt),) if gallery_is_image else ())   # text queries: + cnt
                 for base, gf, gt in self.chunks():
                     n = gf.shape[0]
                     img_f, img_t, txt_f, txt_t = (gf, gt, qf, qt) if gallery_is_image else (qf, qt, gf, gt)
@@ -214,7 +272,10 @@ class LateInteractionIndex:
                     if s_dev is not None:
                         img_f = ops.scale_by_dev(img_f.contiguous(), s_dev)
                     G = similarity_matrix(img_f, txt_f)
-                    ops.maxsim_scores(img_t, txt_t, G, self.alpha, scale, out=view)
+                    if self.token_dtype == "fp8":
+                        ops.maxsim_scores_fp8(img_t, txt_t, G, self.alpha, scale, out=view)
+                    else:
+                        ops.maxsim_scores(img_t, txt_t, G, self.alpha, scale, out=view)
                     ops.topk_merge(view, 1 if gallery_is_image else 0, base, best_val[q0:q1], best_idx[q0:q1])
         pos = best_idx.to(torch.int64)
         if self._running_ids:
@@ -224,7 +285,7 @@ class LateInteractionIndex:
 
     # ------------------------------------------------------------------ through a model
     @classmethod
-    def from_model(cls, model, kind, alpha=None, device=None):
+    def from_model(cls, model, kind, alpha=None, device=None, token_dtype=None):
         """An empty index scored like `model`: a ColXLIP model gives alpha (default: the model's) and logit_scale.exp(); a plain
         CLIP model scores on its global features alone (alpha = 1, the scale applied to the image features as in its
         get_logits)."""
@@ -236,7 +297,8 @@ class LateInteractionIndex:
             raise ValueError("LateInteractionIndex.from_model: a model without token features scores with alpha = 1")
         alpha = (core.alpha if alpha is None else float(alpha)) if late else 1.0
         device = device or core.logit_scale.device
-        return cls(kind, alpha=alpha, scale=float(core.logit_scale.detach().exp()), device=device, prescale=not late)
+        return cls(kind, alpha=alpha, scale=float(core.logit_scale.detach().exp()), device=device, prescale=not late,
+                   token_dtype=token_dtype)
 
     @staticmethod
     def _encode(model, what, batch):
@@ -273,27 +335,39 @@ class LateInteractionIndex:
     # ------------------------------------------------------------------ files
     def save(self, path):
         """meta.json + features.npy [n, E] fp32 + tokens.npy [n, q, E] (bf16 as uint16 bit patterns; absent without tokens) +
-        ids.npy [n] int64, written chunk by chunk."""
+        ids.npy [n] int64, written chunk by chunk.  An fp8 index: tokens.npy holds the e4m3 bytes (uint8), token_exp.npy [n, q]
+        int32 the exponents, token_cnt.npy [n] int32 (text gallery) the packed rows per caption; meta token_dtype = "e4m3"."""
         os.makedirs(path, exist_ok=True)
         e = self._feat[0].shape[1] if self._feat else 0
         meta = {"kind": self.kind, "alpha": self.alpha, "scale": self.scale, "prescale": self.prescale, "n": self._n,
                 "embed_dim": e, "tokens": None, "token_dtype": None, "chunk_items": self._chunk}
         feats = np.lib.format.open_memmap(os.path.join(path, "features.npy"), mode="w+", dtype=np.float32, shape=(self._n, e))
-        toks = None
+        toks, side = None, []
+        fp8 = self.token_dtype == "fp8" and bool(self._tok)
         if self._tok:
             probe, name = _to_numpy(self._tok[0][:0])
-            meta["tokens"], meta["token_dtype"] = list(self._tok[0].shape[1:]), name
+            meta["tokens"], meta["token_dtype"] = list(self._tok[0].shape[1:]), "e4m3" if fp8 else name
             toks = np.lib.format.open_memmap(os.path.join(path, "tokens.npy"), mode="w+", dtype=probe.dtype,
                                              shape=(self._n,) + tuple(self._tok[0].shape[1:]))
         elif os.path.exists(os.path.join(path, "tokens.npy")):
             os.remove(os.path.join(path, "tokens.npy"))
+        for name, store in zip(_FP8_FILES, (self._tok_exp, self._tok_cnt)):
+            if fp8 and store:
+                side.append(np.lib.format.open_memmap(os.path.join(path, name), mode="w+", dtype=np.int32,
+                                                      shape=(self._n,) + tuple(store[0].shape[1:])))
+            elif os.path.exists(os.path.join(path, name)):
+                os.remove(os.path.join(path, name))
         for base, gf, gt in self.chunks():
             feats[base:base + gf.shape[0]] = gf.cpu().numpy()
+            if fp8:
+                gt, *rest = gt
+                for arr, x in zip(side, rest):
+                    arr[base:base + gf.shape[0]] = x.cpu().numpy()
             if toks is not None:
                 toks[base:base + gf.shape[0]] = _to_numpy(gt)[0]
         feats.flush()
-        if toks is not None:
-            toks.flush()
+        for arr in side + ([toks] if toks is not None else []):
+            arr.flush()
         np.save(os.path.join(path, "ids.npy"), self.ids.cpu().numpy())
         with open(os.path.join(path, "meta.json"), "w") as f:
             json.dump(meta, f, indent=1)
@@ -304,20 +378,29 @@ class LateInteractionIndex:
         """The index `save` wrote: the arrays are memory-mapped and copied to `device` `IO_ITEMS` items at a time."""
         with open(os.path.join(path, "meta.json")) as f:
             meta = json.load(f)
-        index = cls(meta["kind"], alpha=meta["alpha"], scale=meta["scale"], device=device, prescale=meta.get("prescale", False))
+        fp8 = meta.get("token_dtype") == "e4m3"
+        index = cls(meta["kind"], alpha=meta["alpha"], scale=meta["scale"], device=device, prescale=meta.get("prescale", False),
+                    token_dtype="fp8" if fp8 else None)
         n = int(meta["n"])
         feats = np.load(os.path.join(path, "features.npy"), mmap_mode="r")
         toks = np.load(os.path.join(path, "tokens.npy"), mmap_mode="r") if meta["tokens"] is not None else None
         ids = np.load(os.path.join(path, "ids.npy"), mmap_mode="r")
-        if feats.shape[0] != n or ids.shape[0] != n or (toks is not None and toks.shape[0] != n):
+        side = []                                    # an fp8 index: the exponents and (text gallery) the counts, kept as saved
+        if fp8:
+            side = [np.load(os.path.join(path, name), mmap_mode="r") for name in _FP8_FILES[:2 if meta["kind"] == "text" else 1]]
+        if feats.shape[0] != n or ids.shape[0] != n or any(a.shape[0] != n for a in side + ([toks] if toks is not None else [])):
             raise ValueError(f"{path}: the arrays do not hold the {n} items meta.json names")
         running = bool(n == 0 or np.array_equal(ids, np.arange(n, dtype=np.int64)))
         step = max(1, int(cls.IO_ITEMS))
         for lo in range(0, n, step):
             hi = min(n, lo + step)
-            index.add(_from_numpy(feats[lo:hi], "float32"),
-                      None if toks is None else _from_numpy(toks[lo:hi], meta["token_dtype"]),
-                      ids=torch.from_numpy(np.array(ids[lo:hi])))
+            if toks is None:
+                tok = None
+            elif fp8:
+                tok = (_from_numpy(toks[lo:hi], "uint8"),) + tuple(_from_numpy(a[lo:hi], "int32") for a in side)
+            else:
+                tok = _from_numpy(toks[lo:hi], meta["token_dtype"])
+            index.add(_from_numpy(feats[lo:hi], "float32"), tok, ids=torch.from_numpy(np.array(ids[lo:hi])))
         index._running_ids = running
         return index
 
@@ -333,6 +416,9 @@ def build_parser():
     parser.add_argument("--out", type=str, default=None, help="results.npz: scores, ids, query_ids")
     parser.add_argument("--save-index", type=str, default=None)
     parser.add_argument("--load-index", type=str, default=None)
+    parser.add_argument("--index-dtype", choices=["model", "fp8"], default="model",
+                        help="token storage of a new index: the model's compute dtype, or e4m3 bytes + one exponent per token "
+                             "(half the bytes, scored on the fp8 MFMA); --load-index takes it from the saved meta.json")
     return parser
 
 
@@ -396,7 +482,8 @@ def run(args):
         alpha = None
         if isinstance(model, ColXLIP):
             alpha = 1.0 if getattr(args, "evaluate_as_original_clip", False) else float(args.alpha)
-        index = LateInteractionIndex.from_model(model, kind, alpha=alpha, device=device)
+        index = LateInteractionIndex.from_model(model, kind, alpha=alpha, device=device,
+                                                token_dtype="fp8" if args.index_dtype == "fp8" else None)
         for batch, ids in gallery():
             index._add_encoded(model, kind, batch, ids)
         if args.save_index:

@@ -460,6 +460,12 @@ int clipx_maxsim_pack_rows(int nt, int n_tok, int e, const void* txt, const int*
                            void* stream);
 int clipx_maxsim_gemm(int R, int ni, int q, int e, const void* packed, const void* img, float* pmax, unsigned short* pidx,
                       int ld, void* stream);
+/* gemm_fp8: the same partials (layout, tie rules) from e4m3 operands on the fp8 MFMA: packed8 [R, e] and img8 [ni * q, e] bytes
+ *   with one power-of-two exponent per row (clipx_quant_rows_e4m3), S[r, c] = 2^(packed_exp[r] + img_exp[c]) * sum packed8 img8,
+ *   the exponents applied BEFORE the maximum.  Needs e % 128 == 0, e >= 256, 16 <= q <= 65535, (ni * q) % 8 == 0 and 16-byte
+ *   aligned operands; anything else is an error (ops.maxsim_scores_fp8 picks the route before it calls).                       */
+int clipx_maxsim_gemm_fp8(int R, int ni, int q, int e, const void* packed8, const int* packed_exp, const void* img8,
+                          const int* img_exp, float* pmax, unsigned short* pidx, int ld, void* stream);
 int clipx_maxsim_finish(int R, int ldp, int r0, int ld, int ni, int q, const float* pmax, const unsigned short* pidx,
                         float* maxvT, unsigned short* argT, void* stream);
 int clipx_maxsim_mean(int nt, int ni, int ld, const int* cu, const float* row_w, const float* maxvT, float* logits,
