@@ -8,8 +8,6 @@ Collectives are torch.distributed (RCCL on MI355X, gloo in CPU tests).
 """
 from typing import Optional
 
-import os
-
 import torch
 import torch.nn as nn
 
@@ -340,8 +338,6 @@ class _MaxSimLogits(torch.autograd.Function):
     maximum + arg-max and the masked mean.  Backward rebuilds the sparse d(S) from the arg-max and reuses the dgrad /
     wgrad GEMMs.  Returns logits_per_text_token [Nt, Ni] (unscaled)."""
 
-    CHUNK_BYTES = 2 << 30
-
     @staticmethod
     def forward(ctx, tok_img, tok_txt):
         ni, q, e = tok_img.shape
@@ -354,7 +350,7 @@ class _MaxSimLogits(torch.autograd.Function):
         img = tok_img.contiguous().view(ni * q, e)
         txt = tok_txt.contiguous().view(nt * n, e)
         esz = 4 if dt == torch.float32 else 2
-        ct = max(1, min(nt, _MaxSimLogits.CHUNK_BYTES // max(1, n * ni * q * esz)))
+        ct = max(1, min(nt, ops.MAXSIM_GENERAL_BYTES // max(1, n * ni * q * esz)))
         if dt == torch.bfloat16:
             ct = max(8, ct // 8 * 8) if nt >= 8 else nt
         logits = torch.empty((nt, ni), dtype=torch.float32, device=img.device)
@@ -423,28 +419,14 @@ class _MaxSimFused(torch.autograd.Function):
         NT / TN GEMM kernels.
     One 4-byte device-to-host read (the packed row count sizes the launches)."""
 
-    CHUNK_BYTES = 2 << 30          # partial maxima of the forward
     P_CHUNK_BYTES = 8 << 30        # d(S) of the backward.  Sized for 288 GB: dText = P img has only E / 256 = 2 tile columns, so a chunk needs
                                    # >= 16.5 k rows to fill the chip with 256x256 tiles (below that the GEMM falls to the 128-row
                                    # one-barrier kernel, 0.75x); 4.5 GB at N = 512 -- one chunk
 
     @staticmethod
     def applies(tok_img, tok_txt) -> bool:
-        ni, q, e = tok_img.shape
-        return (tok_txt.dtype == torch.bfloat16 and tok_img.dtype == torch.bfloat16 and tok_txt.is_cuda and 16 <= q <= 65535
-                and e % 64 == 0 and e >= 128 and (ni * q) % 8 == 0 and os.environ.get("CLIPX_MAXSIM_FUSED", "1") != "0")
-
-    @staticmethod
-    def _chunks(cu_host, limit_rows):
-        """[(m0, m1, r0, r1)]: runs of whole samples with at most `limit_rows` packed rows each (at least one sample)"""
-        out, m0, nt = [], 0, len(cu_host) - 1
-        while m0 < nt:
-            m1 = m0 + 1
-            while m1 < nt and cu_host[m1 + 1] - cu_host[m0] <= limit_rows:
-                m1 += 1
-            out.append((m0, m1, cu_host[m0], cu_host[m1]))
-            m0 = m1
-        return out
+        ni, q, _ = tok_img.shape
+        return ops.maxsim_fused_applies(tok_img, tok_txt) and (ni * q) % 8 == 0
 
     @staticmethod
     def forward(ctx, tok_img, tok_txt):
@@ -460,8 +442,8 @@ class _MaxSimFused(torch.autograd.Function):
         maxvT = torch.empty((ni, ld), dtype=torch.float32, device=dev)
         argT = torch.empty((ni, ld), dtype=torch.int16, device=dev)
         # partial maxima: 6 bytes per (row, slot, segment) -- per (row, image, slot half) below 64 tokens per image; rows in
-        # chunks when that would pass CHUNK_BYTES
-        rows_per = max(256, (_MaxSimFused.CHUNK_BYTES // (6 * prow)) // 256 * 256)
+        # chunks when that would pass ops.MAXSIM_PARTIAL_BYTES
+        rows_per = max(256, (ops.MAXSIM_PARTIAL_BYTES // (6 * prow)) // 256 * 256)
         for r0 in range(0, R, rows_per):
             rc = min(rows_per, R - r0)
             ldp = (rc + 255) // 256 * 256

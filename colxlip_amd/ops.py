@@ -913,25 +913,28 @@ def maxsim_scatter(dlogits, inv_count, arg, n_tok, q, dtype, want_transpose):
 
 
 # fused form (bf16 tokens, >= 16 tokens per image): include/clipx.h "Fused MaxSim"
-def maxsim_pack_text(txt):
-    """txt [nt, n, e] bf16 -> (cu int32 [nt+1] on the device, R = packed rows; one 4-byte read-back).  Trailing positions of a
-    sample that are bitwise equal to its last position are folded into one representative row."""
+def _maxsim_count_text(txt):
+    """txt [nt, n, e] bf16 -> (cnt int32 [nt], cu int32 [nt + 1]) on the device: the one launch of `clipx_maxsim_pack_text`"""
     nt, n, e = txt.shape
     cnt = torch.empty((nt,), dtype=torch.int32, device=txt.device)
     cu = torch.empty((nt + 1,), dtype=torch.int32, device=txt.device)
     check(_lib.lib().clipx_maxsim_pack_text(nt, n, e, _p(_c(txt)), _p(cnt), _p(cu), _stream()))
-    return cu, int(cu[nt].item())
+    return cnt, cu
+
+
+def maxsim_pack_text(txt):
+    """txt [nt, n, e] bf16 -> (cu int32 [nt+1] on the device, R = packed rows; one 4-byte read-back).  Trailing positions of a
+    sample that are bitwise equal to its last position are folded into one representative row."""
+    _, cu = _maxsim_count_text(txt)
+    return cu, int(cu[txt.shape[0]].item())
 
 
 def maxsim_text_counts(txt):
     """txt [nt, n, e] bf16 -> cnt int32 [nt]: the packed rows per sample as `maxsim_pack_text` counts them (leading rows + one
-    representative of the bitwise-equal tail), without the read-back."""
-    nt, n, e = txt.shape
-    cnt = torch.empty((nt,), dtype=torch.int32, device=txt.device)
-    cu = torch.empty((nt + 1,), dtype=torch.int32, device=txt.device)
-    if nt:
-        check(_lib.lib().clipx_maxsim_pack_text(nt, n, e, _p(_c(txt)), _p(cnt), _p(cu), _stream()))
-    return cnt
+    representative of the bitwise-equal tail), without the read-back.  No samples: no launch."""
+    if txt.shape[0] == 0:
+        return torch.empty((0,), dtype=torch.int32, device=txt.device)
+    return _maxsim_count_text(txt)[0]
 
 
 def maxsim_pack_rows(txt, cu, R):
@@ -1002,6 +1005,8 @@ def retrieval_rank(scores, tgt_off, tgt_idx):
 MAXSIM_OPERAND_BYTES = (1 << 31) - 1     # one image chunk of the MaxSim GEMM stays addressable through a 2-GiB buffer descriptor
 MAXSIM_MAX_IMAGES = 65535                # images per chunk
 MAXSIM_TARGET_ROWS = 4096                # an image chunk is shrunk until a text chunk of this many packed rows fits the partials
+MAXSIM_PARTIAL_BYTES = 2 << 30           # partial maxima (pmax + pidx) of one MaxSim GEMM: here and in the forward of loss._MaxSimFused
+MAXSIM_GENERAL_BYTES = 2 << 30           # similarities of one chunk of the general route: here and in loss._MaxSimLogits
 
 
 def maxsim_partial_ld(rows: int) -> int:
@@ -1068,48 +1073,71 @@ def maxsim_score_fold(nm, ni, q, ldp, rbase, cu, m0, row_w, pmax, G, scores, alp
     return scores
 
 
+def maxsim_gemm_takes(q: int, e: int, elem_bytes: int) -> bool:
+    """whether the MaxSim GEMM takes `q` tokens per image of `e` elements of `elem_bytes` bytes (2: bf16, 1: e4m3)"""
+    # the ping-pong engine (csrc/gemm_nt_pp.h) walks an operand row in k-steps of 128 bytes, 64 bf16 or 128 e4m3 elements, and its
+    # pipeline needs at least two of them
+    row_bytes = e * elem_bytes
+    return 16 <= q <= 65535 and row_bytes % 128 == 0 and row_bytes >= 256
+
+
 def maxsim_fused_applies(tok_img, tok_txt) -> bool:
     """the shapes `_MaxSimFused.applies` takes, without its image-count alignment (the chunk plan pads the last chunk)"""
     ni, q, e = tok_img.shape
-    return (tok_txt.dtype == torch.bfloat16 and tok_img.dtype == torch.bfloat16 and tok_txt.is_cuda and 16 <= q <= 65535
-            and e % 64 == 0 and e >= 128 and os.environ.get("CLIPX_MAXSIM_FUSED", "1") != "0")
+    return (tok_txt.dtype == torch.bfloat16 and tok_img.dtype == torch.bfloat16 and tok_txt.is_cuda
+            and maxsim_gemm_takes(q, e, 2) and os.environ.get("CLIPX_MAXSIM_FUSED", "1") != "0")
 
 
-def _maxsim_scores_fused(tok_img, tok_txt, G, alpha, scale, out):
-    from .loss import _MaxSimFused
-    ni, q, e = tok_img.shape
-    dev = tok_img.device
-    img = tok_img.contiguous().view(ni * q, e)
-    txt = tok_txt.contiguous()
+def _pack_text(txt):
+    """bf16 text [nt, n, e] -> (packed [R, e], None, cu [nt + 1] int32, row_w [R]): the text operand of `_maxsim_scores_fused`"""
+    txt = txt.contiguous()
     cu, R = maxsim_pack_text(txt)
     packed, _, row_w = maxsim_pack_rows(txt, cu, R)
-    image_chunks, text_chunks = plan_maxsim_chunks(ni, q, e, cu.cpu().tolist(), _MaxSimFused.CHUNK_BYTES)
+    return packed, None, cu, row_w
+
+
+def _rows_padded(x, r0, r1, rows):
+    """x[r0:r1] as `rows` >= r1 - r0 rows: the view itself, or a copy with zero rows (byte 0, exponent 0) behind it"""
+    if rows == r1 - r0:
+        return x[r0:r1]
+    op = torch.zeros((rows,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+    op[:r1 - r0] = x[r0:r1]
+    return op
+
+
+def _maxsim_scores_fused(img_rows, img_exp, packed, packed_exp, cu, row_w, ni, q, G, alpha, scale, out):
+    """The fused route of `maxsim_scores` (exponents None: bf16 rows, `maxsim_gemm`) and of `maxsim_scores_fp8` (e4m3 bytes with
+    one int32 exponent per row, `maxsim_gemm_fp8`).  img_rows [ni * q, e], packed [R, e]: the rows of `maxsim_pack_rows`."""
+    e = img_rows.shape[1]
+    dev = img_rows.device
+    image_chunks, text_chunks = plan_maxsim_chunks(ni, q, e, cu.cpu().tolist(), MAXSIM_PARTIAL_BYTES,
+                                                   elem_bytes=img_rows.element_size())
     cmax = max(c for _, _, c in image_chunks)
     ldmax = maxsim_partial_ld(max(r1 - r0 for _, _, r0, r1 in text_chunks))
     prow = maxsim_partial_rows(cmax, q)
     pmax = torch.empty((prow * ldmax,), dtype=torch.float32, device=dev)
     pidx = torch.empty((prow * ldmax,), dtype=torch.int16, device=dev)
     for k0, k1, ci in image_chunks:
-        if ci == k1 - k0:
-            op = img[k0 * q:k1 * q]
-        else:                                                   # zero images behind the last ones: their columns are never folded
-            op = torch.zeros((ci * q, e), dtype=img.dtype, device=dev)
-            op[:(k1 - k0) * q] = img[k0 * q:k1 * q]
+        # zero images behind the last ones of a padded chunk: their columns are never folded
+        op = _rows_padded(img_rows, k0 * q, k1 * q, ci * q)
+        op_exp = None if img_exp is None else _rows_padded(img_exp, k0 * q, k1 * q, ci * q)
         for m0, m1, r0, r1 in text_chunks:
             ldp = maxsim_partial_ld(r1 - r0)
-            maxsim_gemm(packed[r0:r1], op, ci, q, pmax, pidx, ldp)
+            if img_exp is None:
+                maxsim_gemm(packed[r0:r1], op, ci, q, pmax, pidx, ldp)
+            else:
+                maxsim_gemm_fp8(packed[r0:r1], packed_exp[r0:r1], op, op_exp, ci, q, pmax, pidx, ldp)
             maxsim_score_fold(m1 - m0, k1 - k0, q, ldp, r0, cu, m0, row_w, pmax, None if G is None else G[k0:k1, m0:m1],
                               out[k0:k1, m0:m1], alpha, scale)
     return out
 
 
 def _maxsim_scores_general(tok_img, tok_txt, G, alpha, scale, out):
-    from .loss import _MaxSimLogits
     ni, q, e = tok_img.shape
     nt, n, _ = tok_txt.shape
     img = tok_img.contiguous().float().view(ni * q, e)
     txt = tok_txt.contiguous().float().view(nt * n, e)
-    limit = _MaxSimLogits.CHUNK_BYTES
+    limit = MAXSIM_GENERAL_BYTES
     ci = max(1, min(ni, limit // max(1, 4 * n * q)))           # images per chunk: one sample's similarities fit
     ct = max(1, min(nt, limit // max(1, 4 * n * ci * q)))
     for k0 in range(0, ni, ci):
@@ -1130,6 +1158,18 @@ def _maxsim_scores_general(tok_img, tok_txt, G, alpha, scale, out):
     return out
 
 
+def _maxsim_scores_frame(G, out, ni, nt, device):
+    """the checks of `G` and `out` [ni, nt] fp32 that both scorers share -> (G with a unit column stride, out: allocated if None)"""
+    if G is not None:
+        assert G.shape == (ni, nt) and G.dtype == torch.float32
+        if G.stride(1) != 1:
+            G = G.contiguous()
+    if out is None:
+        out = torch.empty((ni, nt), dtype=torch.float32, device=device)
+    assert out.shape == (ni, nt) and out.dtype == torch.float32 and out.stride(1) == 1
+    return G, out
+
+
 def maxsim_scores(tok_img, tok_txt, G, alpha, scale, out=None):
     """Late-interaction scores without autograd: scores [ni, nt] (fp32, image-major) =
         scale * (alpha * G + (1 - alpha) * MaxSim(tok_img [ni, q, e], tok_txt [nt, n, e])^T)
@@ -1146,45 +1186,53 @@ def maxsim_scores(tok_img, tok_txt, G, alpha, scale, out=None):
         ni, q, e = tok_img.shape
         nt, n, e2 = tok_txt.shape
         assert e == e2 and tok_img.dtype == tok_txt.dtype and tok_img.is_cuda
-    if G is not None:
-        assert G.shape == (ni, nt) and G.dtype == torch.float32
-        if G.stride(1) != 1:
-            G = G.contiguous()
-    if out is None:
-        out = torch.empty((ni, nt), dtype=torch.float32, device=G.device if G is not None else tok_img.device)
-    assert out.shape == (ni, nt) and out.dtype == torch.float32 and out.stride(1) == 1
+    G, out = _maxsim_scores_frame(G, out, ni, nt, G.device if G is not None else tok_img.device)
     with torch.no_grad():
         if alpha == 1.0:
             for k0 in range(0, ni, 4 * MAXSIM_MAX_IMAGES):
                 k1 = min(ni, k0 + 4 * MAXSIM_MAX_IMAGES)
                 maxsim_score_fold(nt, k1 - k0, 0, 0, 0, None, 0, None, None, G[k0:k1], out[k0:k1], 1.0, scale)
             return out
+        tok_img, tok_txt = tok_img.detach(), tok_txt.detach()
         if maxsim_fused_applies(tok_img, tok_txt):
-            return _maxsim_scores_fused(tok_img.detach(), tok_txt.detach(), G, alpha, scale, out)
-        return _maxsim_scores_general(tok_img.detach(), tok_txt.detach(), G, alpha, scale, out)
+            return _maxsim_scores_fused(tok_img.contiguous().view(ni * q, e), None, *_pack_text(tok_txt), ni, q, G, alpha, scale, out)
+        return _maxsim_scores_general(tok_img, tok_txt, G, alpha, scale, out)
 
 
 # ------------------------------------------------------------------ late-interaction scoring on e4m3 tokens
 # Either side of `maxsim_scores_fp8` is a bf16 tensor (quantised on the fly) or its stored form: an image side (bytes [ni, q, e]
 # uint8, exp [ni, q] int32), a text side (bytes [nt, n, e], exp [nt, n], cnt [nt] int32) with cnt = `maxsim_text_counts` of the
-# bf16 rows.  The quantiser works row by row, so the packed rows of a stored text side are the rows the on-the-fly route
-# quantises after packing, byte for byte.
-def _fp8_side(x):
-    """(tensor that carries shape [items, tokens, e] and device, stored?)"""
+# bf16 rows, as a tuple or a list.  The quantiser works row by row, so the packed rows of a stored text side are the rows the
+# on-the-fly route quantises after packing, byte for byte.
+def _image_side(x):
+    """image side -> (tokens [ni, q, e] bf16 or bytes uint8, exp [ni, q] int32 of the stored form or None)"""
     if isinstance(x, (tuple, list)):
-        return x[0], True
-    return x, False
+        return x[0], x[1]
+    return x, None
+
+
+def _text_side(x):
+    """text side -> (tokens [nt, n, e] bf16 or bytes uint8, exp [nt, n] of the stored form or None, cnt [nt] or None)"""
+    if isinstance(x, (tuple, list)):
+        return x[0], x[1], x[2] if len(x) > 2 else None
+    return x, None, None
 
 
 def maxsim_fp8_applies(img, txt) -> bool:
     """whether `maxsim_scores_fp8` runs the fp8 MaxSim GEMM on these sides (else: the general fp32 route on dequantised values)"""
-    ti, si = _fp8_side(img)
-    tt, st = _fp8_side(txt)
+    ti, ie = _image_side(img)
+    tt, te, _ = _text_side(txt)
     ni, q, e = ti.shape
-    ok_i = ti.dtype == (torch.uint8 if si else torch.bfloat16)
-    ok_t = tt.dtype == (torch.uint8 if st else torch.bfloat16)
-    return (ok_i and ok_t and ti.is_cuda and tt.is_cuda and 16 <= q <= 65535 and e % 128 == 0 and e >= 256
+    ok_i = ti.dtype == (torch.bfloat16 if ie is None else torch.uint8)
+    ok_t = tt.dtype == (torch.bfloat16 if te is None else torch.uint8)
+    return (ok_i and ok_t and ti.is_cuda and tt.is_cuda and maxsim_gemm_takes(q, e, 1)
             and os.environ.get("CLIPX_MAXSIM_FUSED", "1") != "0")
+
+
+def _pack_text_quantised(txt):
+    """bf16 text -> (packed8 [R, e], packed_exp [R], cu, row_w): the packed rows, quantised row by row"""
+    packed, _, cu, row_w = _pack_text(txt)
+    return quant_rows_e4m3(packed) + (cu, row_w)
 
 
 def _fp8_pack_stored_text(t8, te, cnt):
@@ -1196,42 +1244,6 @@ def _fp8_pack_stored_text(t8, te, cnt):
     packed, row_m, row_w = maxsim_pack_rows(t8.contiguous().view(torch.bfloat16), cu, R)        # a byte row as e / 2 bf16: a copy
     pos = torch.arange(R, dtype=torch.int64, device=t8.device) - cu[:-1].long()[row_m.long()]
     return packed.view(torch.uint8), te.contiguous().view(-1)[row_m.long() * n + pos].contiguous(), cu, row_w
-
-
-def _maxsim_scores_fp8_fused(img, txt, G, alpha, scale, out):
-    from .loss import _MaxSimFused
-    ti, stored_i = _fp8_side(img)
-    ni, q, e = ti.shape
-    dev = ti.device
-    i8, ie = (img[0], img[1]) if stored_i else quant_tokens_e4m3(img)
-    i8, ie = i8.contiguous().view(ni * q, e), ie.contiguous().view(ni * q)
-    if isinstance(txt, (tuple, list)):
-        p8, pe, cu, row_w = _fp8_pack_stored_text(*txt)
-    else:
-        t = txt.contiguous()
-        cu, R = maxsim_pack_text(t)
-        packed, _, row_w = maxsim_pack_rows(t, cu, R)
-        p8, pe = quant_rows_e4m3(packed)
-    image_chunks, text_chunks = plan_maxsim_chunks(ni, q, e, cu.cpu().tolist(), _MaxSimFused.CHUNK_BYTES, elem_bytes=1)
-    cmax = max(c for _, _, c in image_chunks)
-    ldmax = maxsim_partial_ld(max(r1 - r0 for _, _, r0, r1 in text_chunks))
-    prow = maxsim_partial_rows(cmax, q)
-    pmax = torch.empty((prow * ldmax,), dtype=torch.float32, device=dev)
-    pidx = torch.empty((prow * ldmax,), dtype=torch.int16, device=dev)
-    for k0, k1, ci in image_chunks:
-        if ci == k1 - k0:
-            op8, ope = i8[k0 * q:k1 * q], ie[k0 * q:k1 * q]
-        else:                                                   # zero images (byte 0, exponent 0) behind the last ones: never folded
-            op8 = torch.zeros((ci * q, e), dtype=torch.uint8, device=dev)
-            ope = torch.zeros((ci * q,), dtype=torch.int32, device=dev)
-            op8[:(k1 - k0) * q] = i8[k0 * q:k1 * q]
-            ope[:(k1 - k0) * q] = ie[k0 * q:k1 * q]
-        for m0, m1, r0, r1 in text_chunks:
-            ldp = maxsim_partial_ld(r1 - r0)
-            maxsim_gemm_fp8(p8[r0:r1], pe[r0:r1], op8, ope, ci, q, pmax, pidx, ldp)
-            maxsim_score_fold(m1 - m0, k1 - k0, q, ldp, r0, cu, m0, row_w, pmax, None if G is None else G[k0:k1, m0:m1],
-                              out[k0:k1, m0:m1], alpha, scale)
-    return out
 
 
 def maxsim_scores_fp8(img, txt, G, alpha, scale, out=None):
@@ -1246,24 +1258,22 @@ def maxsim_scores_fp8(img, txt, G, alpha, scale, out=None):
     alpha, scale = float(alpha), float(scale)
     if alpha == 1.0:
         return maxsim_scores(None, None, G, 1.0, scale, out=out)
-    ti, stored_i = _fp8_side(img)
-    tt, stored_t = _fp8_side(txt)
+    ti, ie = _image_side(img)
+    tt, te, cnt = _text_side(txt)
     ni, q, e = ti.shape
     nt, n, e2 = tt.shape
     assert e == e2 and ti.device == tt.device
-    if G is not None:
-        assert G.shape == (ni, nt) and G.dtype == torch.float32
-        if G.stride(1) != 1:
-            G = G.contiguous()
-    if out is None:
-        out = torch.empty((ni, nt), dtype=torch.float32, device=ti.device)
-    assert out.shape == (ni, nt) and out.dtype == torch.float32 and out.stride(1) == 1
+    G, out = _maxsim_scores_frame(G, out, ni, nt, ti.device)
     with torch.no_grad():
-        if maxsim_fp8_applies(img, txt):
-            return _maxsim_scores_fp8_fused(img, txt, G, alpha, scale, out)
-        i8, ie = (img[0], img[1]) if stored_i else quant_tokens_e4m3(img.detach())
-        t8, te = (txt[0], txt[1]) if stored_t else quant_tokens_e4m3(txt.detach())
-        return _maxsim_scores_general(dequant_tokens_e4m3(i8, ie), dequant_tokens_e4m3(t8, te), G, alpha, scale, out)
+        fused = maxsim_fp8_applies(img, txt)
+        if ie is None:
+            ti, ie = quant_tokens_e4m3(ti.detach())
+        if fused:
+            text = _pack_text_quantised(tt.detach()) if te is None else _fp8_pack_stored_text(tt, te, cnt)
+            return _maxsim_scores_fused(ti.contiguous().view(ni * q, e), ie.contiguous().view(ni * q), *text, ni, q, G, alpha, scale, out)
+        if te is None:
+            tt, te = quant_tokens_e4m3(tt.detach())
+        return _maxsim_scores_general(dequant_tokens_e4m3(ti, ie), dequant_tokens_e4m3(tt, te), G, alpha, scale, out)
 
 
 # ------------------------------------------------------------------ streaming top-k (late-interaction search)

@@ -209,9 +209,17 @@ class LateInteractionIndex:
                              "(or fp32, rounded to bf16)")
         if tokens.dim() != 3 or tokens.shape[0] != n:
             raise ValueError("LateInteractionIndex.add: tokens must be [n, q, E] with the features' n and E")
-        tokens = tokens.detach().to(self.device).to(torch.bfloat16).contiguous()
+        return self._scorer_form(tokens, self.kind)
+
+    def _scorer_form(self, tokens, side):
+        """tokens [n, q, E] of `side` ("image" or "text") -> on the device, in the form the scorer takes: as they are, or for an fp8
+        index (bytes, exp) of their bf16 cast, for a text side (bytes, exp, cnt)"""
+        tokens = tokens.detach().to(self.device)
+        if self.token_dtype != "fp8":
+            return tokens
+        tokens = tokens.to(torch.bfloat16).contiguous()
         out = ops.quant_tokens_e4m3(tokens)
-        return out + (ops.maxsim_text_counts(tokens),) if want == 3 else out
+        return out + (ops.maxsim_text_counts(tokens),) if side == "text" else out
 
     def chunks(self):
         """[(position of the first item, features [n, E], tokens [n, q, E] or None)] over the stored items; an fp8 index yields
@@ -257,14 +265,12 @@ class LateInteractionIndex:
         s_dev = torch.tensor([self.scale], dtype=torch.float32, device=dev) if self.prescale else None
         scale = 1.0 if self.prescale else self.scale
         from .train import similarity_matrix
+        score = ops.maxsim_scores_fp8 if self.token_dtype == "fp8" else ops.maxsim_scores      # looked up per search
         with torch.no_grad():
             for q0 in range(0, nq, qchunk):
                 q1 = min(nq, q0 + qchunk)
                 qf = features[q0:q1]
-                qt = None if tokens is None else tokens[q0:q1].detach().to(dev)
-                if qt is not None and self.token_dtype == "fp8":
-                    qt = qt.to(torch.bfloat16).contiguous()
-                    qt = ops.quant_tokens_e4m3(qt) + ((ops.maxsim_text_counts(qt),) if gallery_is_image else ())   # text queries: + cnt
+                qt = None if tokens is None else self._scorer_form(tokens[q0:q1], "text" if gallery_is_image else "image")
                 for base, gf, gt in self.chunks():
                     n = gf.shape[0]
                     img_f, img_t, txt_f, txt_t = (gf, gt, qf, qt) if gallery_is_image else (qf, qt, gf, gt)
@@ -272,10 +278,7 @@ class LateInteractionIndex:
                     if s_dev is not None:
                         img_f = ops.scale_by_dev(img_f.contiguous(), s_dev)
                     G = similarity_matrix(img_f, txt_f)
-                    if self.token_dtype == "fp8":
-                        ops.maxsim_scores_fp8(img_t, txt_t, G, self.alpha, scale, out=view)
-                    else:
-                        ops.maxsim_scores(img_t, txt_t, G, self.alpha, scale, out=view)
+                    score(img_t, txt_t, G, self.alpha, scale, out=view)
                     ops.topk_merge(view, 1 if gallery_is_image else 0, base, best_val[q0:q1], best_idx[q0:q1])
         pos = best_idx.to(torch.int64)
         if self._running_ids:

@@ -1,23 +1,14 @@
 """CPU-side checks of late-interaction retrieval: the chunk plan of `ops.maxsim_scores` (a pure function), the
 `--evaluate-as-original-clip` flag, and the binding of the new C entry point."""
 import ctypes
-import itertools
 
 import pytest
 
 from colxlip_amd import _lib, ops
 from colxlip_amd.params import parse_args
+from tests.late_interaction_ref import cu_of as _cu, packed_counts as _counts
 
 GIB2 = (1 << 31) - 1
-
-
-def _cu(counts):
-    return [0] + list(itertools.accumulate(counts))
-
-
-def _counts(nt, n, seed):
-    """packed rows per sample: EOT-shaped lengths in [1, n], deterministic"""
-    return [1 + (seed + 37 * m * m + 11 * m) % n for m in range(nt)]
 
 
 PLAN_GRID = [
@@ -90,3 +81,12 @@ def test_score_fold_prototype_resolves():
     assert hasattr(ctypes.CDLL(_lib.lib_path()), "clipx_maxsim_score_fold")
     fn = _lib.lib().clipx_maxsim_score_fold
     assert fn.restype is ctypes.c_int and list(fn.argtypes) == args
+
+
+@pytest.mark.parametrize("q", [15, 16, 63, 64, 65535, 65536])
+@pytest.mark.parametrize("e", [64, 96, 128, 192, 256, 320, 384, 512, 768])
+def test_maxsim_gemm_takes_is_the_two_embed_dim_rules(q, e):
+    """one rule on the bytes of an operand row (a multiple of the 128-byte k-step, at least two of them) against the rules the
+    bf16 and the e4m3 route spelled out before, written out literally"""
+    assert ops.maxsim_gemm_takes(q, e, 2) == (16 <= q <= 65535 and e % 64 == 0 and e >= 128)
+    assert ops.maxsim_gemm_takes(q, e, 1) == (16 <= q <= 65535 and e % 128 == 0 and e >= 256)

@@ -15,13 +15,13 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from colxlip_amd import create_model_and_transforms, ops  # noqa: E402
-from colxlip_amd import loss as LS  # noqa: E402
+from colxlip_amd import ops  # noqa: E402
 from colxlip_amd import train as TR  # noqa: E402
 from colxlip_amd.data import synthetic_retrieval_split  # noqa: E402
 from colxlip_amd.main import main  # noqa: E402
 from colxlip_amd.params import parse_args  # noqa: E402
 from oracle import clip_oracle as O  # noqa: E402
+from tests import late_interaction_ref as R  # noqa: E402
 
 DEV = "cuda"
 MODEL = "ViT-small-test-colxlip"
@@ -39,44 +39,12 @@ FUSED_SHAPES = [(5, 64, 6, 9, 128), (4, 100, 7, 7, 256), (6, 196, 9, 77, 128), (
 SHRUNK = {(5, 64, 6, 9, 128): (2, 16), (4, 100, 7, 7, 256): (2, 16), (6, 196, 9, 77, 128): (4, 96), (5, 100, 7, 7, 256): (2, 16)}
 
 
-def _tokens(ni, q, nt, n, e, seed=None):
-    """Token features built like test_maxsim_fused_vs_torch's: every position at / behind a per-sample EOT is one vector, sample
-    1 has exact-zero rows there, sample 2 keeps distinct rows to the end, and the last sample's EOT is 0: one packed row."""
-    g = torch.Generator().manual_seed(100 + q if seed is None else seed)
-    ti = torch.nn.functional.normalize(torch.randn(ni, q, e, generator=g), dim=-1)
-    tt = torch.nn.functional.normalize(torch.randn(nt, n, e, generator=g), dim=-1)
-    tail = torch.nn.functional.normalize(torch.randn(e, generator=g), dim=-1)
-    for m in range(nt):
-        eot = 2 + (5 * m) % (n - 2)
-        if m == 1:
-            tt[m, eot:] = 0.0
-        elif m == nt - 1:
-            tt[m, :] = tail
-        elif m != 2:
-            tt[m, eot:] = tail
-    return ti, tt
-
-
-def _einsum_ref(ti32, tt32):
-    """reference loss.py:20-46 in fp32 (as tests/test_model_gpu.py:606-609) -> tok [nt, ni]"""
-    sim = torch.einsum('mnd,kqd->mknq', tt32, ti32)
-    mx = sim.max(dim=3)[0]
-    return mx.sum(-1) / ((mx != 0).float().sum(-1) + 1e-8)
-
-
-def _shrink(monkeypatch, ni, q, e, ci, rows):
-    """chunk limits under which the plan holds `ci` images per chunk and at most `rows` packed rows per text chunk"""
-    monkeypatch.setattr(ops, "MAXSIM_OPERAND_BYTES", ci * q * e * 2)
-    monkeypatch.setattr(ops, "MAXSIM_TARGET_ROWS", rows)
-    monkeypatch.setattr(LS._MaxSimFused, "CHUNK_BYTES", ops.maxsim_partial_bytes(ci, q, rows))
-
-
 @pytest.mark.parametrize("ni,q,nt,n,e", FUSED_SHAPES)
 def test_fold_kernel_vs_reference_arithmetic(ni, q, nt, n, e, monkeypatch):
     """The fused route (MaxSim GEMM partials -> clipx_maxsim_score_fold) against the reference's arithmetic in fp32 on the same bf16
     values, bound 2e-5 (the fused forward's bound on tok, tests/test_model_gpu.py:611); image-major output, checked element
     [k, m] against ref[m, k]; then once more with the chunk limits shrunk (>= 2 image chunks, >= 2 text chunks): bit-equal."""
-    ti, tt = _tokens(ni, q, nt, n, e)
+    ti, tt = R.tokens(ni, q, nt, n, e)
     a, b = ti.to(DEV).bfloat16(), tt.to(DEV).bfloat16()
     assert ops.maxsim_fused_applies(a, b)
     calls = []
@@ -85,7 +53,7 @@ def test_fold_kernel_vs_reference_arithmetic(ni, q, nt, n, e, monkeypatch):
     scores = ops.maxsim_scores(a, b, None, 0.0, 1.0)
     assert scores.shape == (ni, nt) and scores.dtype == torch.float32
     assert len(calls) == 1
-    ref = _einsum_ref(a.float(), b.float())                     # [nt, ni]
+    ref = R.einsum_ref(a.float(), b.float())                     # [nt, ni]
     err = max(abs(float(scores[k, m]) - float(ref[m, k])) for k in range(ni) for m in range(nt))
     print(f"fold ({ni},{q},{nt},{n},{e}): max |scores[k,m] - ref[m,k]| = {err:.3e}")
     assert err < 2e-5, err
@@ -94,8 +62,8 @@ def test_fold_kernel_vs_reference_arithmetic(ni, q, nt, n, e, monkeypatch):
     cu = cu.cpu().tolist()
     assert cu[nt] - cu[nt - 1] == 1 and cu[3] - cu[2] == n
     ci, rows = SHRUNK[(ni, q, nt, n, e)]
-    _shrink(monkeypatch, ni, q, e, ci, rows)
-    image_chunks, text_chunks = ops.plan_maxsim_chunks(ni, q, e, cu, LS._MaxSimFused.CHUNK_BYTES)
+    R.shrink(monkeypatch, q, e, ci, rows)
+    image_chunks, text_chunks = ops.plan_maxsim_chunks(ni, q, e, cu, ops.MAXSIM_PARTIAL_BYTES)
     assert len(image_chunks) >= 2 and len(text_chunks) >= 2
     assert text_chunks[-1][3] - text_chunks[-1][2] < max(r1 - r0 for _, _, r0, r1 in text_chunks)
     if ni % ci:
@@ -109,7 +77,7 @@ def test_fold_kernel_vs_reference_arithmetic(ni, q, nt, n, e, monkeypatch):
 def test_combine_with_global_similarities():
     """scores = scale * (alpha * G + (1 - alpha) * tok^T) with random G; alpha = 1 is scale * G bit for bit."""
     ni, q, nt, n, e = 5, 64, 6, 9, 128
-    ti, tt = _tokens(ni, q, nt, n, e)
+    ti, tt = R.tokens(ni, q, nt, n, e)
     a, b = ti.to(DEV).bfloat16(), tt.to(DEV).bfloat16()
     G = torch.randn(ni, nt, generator=torch.Generator().manual_seed(5)).to(DEV)
     scale = 14.0
@@ -129,13 +97,13 @@ def test_combine_with_global_similarities():
 def test_general_route(dtype, ni, q, nt, n, e, monkeypatch):
     """fp32 tokens, and bf16 tokens with q < 64: fp32 arithmetic on gemm_f32 + maxsim_reduce + masked_mean, 2e-5 against the einsum
     reference on the same values (bf16 inputs are cast up: the same numbers, fp32 arithmetic); chunked = unchunked."""
-    ti, tt = _tokens(ni, q, nt, n, e)
+    ti, tt = R.tokens(ni, q, nt, n, e)
     a, b = ti.to(DEV).to(dtype), tt.to(DEV).to(dtype)
     assert not ops.maxsim_fused_applies(a, b)
     monkeypatch.setattr(ops, "maxsim_score_fold", lambda *args: pytest.fail("the fused route ran"))
     scores = ops.maxsim_scores(a, b, None, 0.0, 1.0)
     assert scores.shape == (ni, nt)
-    ref = _einsum_ref(a.float(), b.float())
+    ref = R.einsum_ref(a.float(), b.float())
     err = float((scores - ref.t()).abs().max())
     print(f"general route {dtype}: max error {err:.3e}")
     assert err < 2e-5, err
@@ -143,27 +111,15 @@ def test_general_route(dtype, ni, q, nt, n, e, monkeypatch):
     want = 14.0 * (0.3 * G + 0.7 * ref.t())
     got = ops.maxsim_scores(a, b, G, 0.3, 14.0)
     assert float((got - want).abs().max()) < 14.0 * 2e-5
-    monkeypatch.setattr(LS._MaxSimLogits, "CHUNK_BYTES", 4 * n * 2 * q)             # 2 images x 1 sample per chunk
+    monkeypatch.setattr(ops, "MAXSIM_GENERAL_BYTES", 4 * n * 2 * q)             # 2 images x 1 sample per chunk
     assert float((ops.maxsim_scores(a, b, G, 0.3, 14.0) - got).abs().max()) < 1e-5
-
-
-def _colxlip_sd(cfg):
-    sd = O.perturb_state_dict(O.init_state_dict(cfg, seed=3), seed=4)
-    sd.update(O.perturb_state_dict(O.init_colxlip_heads(cfg, seed=5), seed=6))
-    return sd
-
-
-def _model(name, sd, precision):
-    model, _, _ = create_model_and_transforms(name, precision=precision, device=DEV, output_dict=True)
-    model.load_state_dict({k: v.clone() for k, v in sd.items()}, strict=True)
-    return model
 
 
 def test_colxlip_get_logits_matches_oracle():
     """ColXLIP.get_logits on 6 images x 9 texts against the oracle's towers + colbert_similarity, bound 1e-4 (that of
     test_clip_get_logits_matches_oracle): without grad (ops.maxsim_scores) and with grad (the differentiable pieces)."""
-    sd = _colxlip_sd(CFG)
-    model = _model(MODEL, sd, "fp32")
+    sd = R.model_state(CFG)
+    model = R.build_model(MODEL, sd, "fp32")
     image, text = O.synthetic_batch(CFG, 9, seed=31)
     image = image[:6]
     ref = O.colxlip_forward(sd, image, text, CFG)
@@ -261,7 +217,7 @@ def _check_against_oracle_scores(got, prefix, oracle_scores, txt2img, img2txt, w
 @pytest.fixture(scope="module")
 def coco_case():
     """The 24 x 5 split, ViT-small-test-colxlip weights, and the oracle's global and token similarities on it (computed once)."""
-    sd = _colxlip_sd(CFG)
+    sd = R.model_state(CFG)
     split = synthetic_retrieval_split(24, 5, CFG.image_size, CFG.context_length, CFG.vocab_size, seed=99, device="cuda", batch_size=7)
     txt, img, _, _ = split
     images = torch.cat([x for x, _ in img.dataloader]).float().cpu()
@@ -284,7 +240,7 @@ def test_evaluate_colxlip_fp32(coco_case, caplog, tmp_path):
     c = coco_case
     split = c["split"]
     txt, img, _, _ = split
-    model = _model(MODEL, c["sd"], "fp32")
+    model = R.build_model(MODEL, c["sd"], "fp32")
     model.train()
     args = _args(MODEL, "fp32", ["--alpha", "0.5", "--epochs", "3", "--val-frequency", "2"])
     args.save_logs, args.checkpoint_path = True, str(tmp_path)
@@ -316,7 +272,7 @@ def test_evaluate_colxlip_fp32(coco_case, caplog, tmp_path):
 def test_evaluate_colxlip_bf16(coco_case):
     """bf16 towers and tokens feed rounded features into the same ranking: the slack of test_evaluate_matches_oracle_pipeline."""
     c = coco_case
-    model = _model(MODEL, c["sd"], "bf16")
+    model = R.build_model(MODEL, c["sd"], "bf16")
     args = _args(MODEL, "bf16", ["--alpha", "0.5"])
     got = TR.evaluate(model, {"retrieval_coco": c["split"]}, 1, args)
     want = O.retrieval_metrics(c["scores"](0.5), c["txt2img"], c["img2txt"])
@@ -332,7 +288,7 @@ def test_evaluate_as_original_clip(coco_case):
     """--evaluate-as-original-clip scores a ColXLIP model on its global features only (the reference's `original_clip` mode):
     the existing global-only oracle's metrics, and key for key those of --alpha 1.0."""
     c = coco_case
-    model = _model(MODEL, c["sd"], "fp32")
+    model = R.build_model(MODEL, c["sd"], "fp32")
     got = TR.evaluate(model, {"retrieval_coco": c["split"]}, 1, _args(MODEL, "fp32", ["--alpha", "0.5", "--evaluate-as-original-clip"]))
     alpha1 = TR.evaluate(model, {"retrieval_coco": c["split"]}, 1, _args(MODEL, "fp32", ["--alpha", "1.0"]))
     assert got == alpha1 and len(got) == 13
@@ -346,19 +302,19 @@ def test_evaluate_as_original_clip(coco_case):
 def test_fused_route_through_a_model(monkeypatch):
     """ViT-q64-test-colxlip (128 px / patch 16: 64 image tokens, embed dim 128) in bf16 takes the fused route inside evaluate();
     its scores within 2e-2 (the bf16-vs-fp32 MaxSim bound, tests/test_model_gpu.py:572) of the fp32 run of the same model."""
-    sd = _colxlip_sd(Q64)
+    sd = R.model_state(Q64)
     split = synthetic_retrieval_split(16, 3, Q64.image_size, Q64.context_length, Q64.vocab_size, seed=7, device="cuda", batch_size=8)
     txt, img, _, _ = split
     calls = []
     fold = ops.maxsim_score_fold
     monkeypatch.setattr(ops, "maxsim_score_fold", lambda *args: (calls.append(args[:2]), fold(*args))[1])
-    m16 = _model(Q64_MODEL, sd, "bf16")
+    m16 = R.build_model(Q64_MODEL, sd, "bf16")
     got = TR.evaluate(m16, {"retrieval_coco": split}, 1, _args(Q64_MODEL, "bf16", ["--alpha", "0.5"]))
     assert len(calls) == 1 and calls[0] == (48, 16)
     assert got["retrieval_coco_num_text_samples"] == 48 and 0.0 <= got["retrieval_coco_text_to_image_R@1"] <= 1.0
     s16, _, _ = TR.late_interaction_scores(m16.eval(), txt.dataloader, img.dataloader, torch.device("cuda"), TR.get_input_dtype("bf16"), alpha=0.5)
     assert len(calls) == 2
-    m32 = _model(Q64_MODEL, sd, "fp32").eval()
+    m32 = R.build_model(Q64_MODEL, sd, "fp32").eval()
     s32, _, _ = TR.late_interaction_scores(m32, txt.dataloader, img.dataloader, torch.device("cuda"), torch.float32, alpha=0.5)
     assert len(calls) == 2                                      # fp32 tokens: the general route
     # the fused route against fp32 arithmetic on the bf16 model's own tokens (the general route): the fold bound, times the scale

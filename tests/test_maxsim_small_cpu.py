@@ -5,7 +5,8 @@ import pytest
 import torch
 
 from colxlip_amd import create_model_and_transforms, get_model_config, ops
-from tests.test_late_interaction_cpu import GIB2, PLAN_GRID, _counts, _cu
+from tests.late_interaction_ref import cu_of as _cu, packed_counts as _counts
+from tests.test_late_interaction_cpu import GIB2, PLAN_GRID
 
 SMALL_Q = (16, 17, 24, 49, 63)
 

@@ -13,7 +13,8 @@ pytestmark = pytest.mark.gpu
 from colxlip_amd import ops  # noqa: E402
 from colxlip_amd import loss as LS  # noqa: E402
 from oracle import clip_oracle as O  # noqa: E402
-from tests.test_late_interaction_gpu import _colxlip_sd, _einsum_ref, _model, _shrink, _tokens  # noqa: E402
+from tests import late_interaction_ref as R  # noqa: E402
+from tests.late_interaction_ref import Q49, Q49_MODEL  # noqa: E402
 
 DEV = "cuda"
 
@@ -85,7 +86,7 @@ def test_ties_go_to_the_first_token(q, k):
     first partial across slots, like torch.max), and its logits are those of an image that holds the vector once."""
     ni, nt, n, e = 8, 6, 9, 128
     assert k * q < 64 < (k + 1) * q - 1
-    ti, tt = _tokens(ni, q, nt, n, e)
+    ti, tt = R.tokens(ni, q, nt, n, e)
     ti[k, :] = ti[k, 0].clone()
     a = ti.to(DEV).bfloat16().requires_grad_(True)
     b = tt.to(DEV).bfloat16().requires_grad_(True)
@@ -95,7 +96,7 @@ def test_ties_go_to_the_first_token(q, k):
     out.backward(gout)
     ga = a.grad.float()
     assert float(ga[k, 1:].abs().max()) == 0.0 and float(ga[k, 0].norm()) > 0
-    ref = _einsum_ref(a.detach().float(), b.detach().float())              # [nt, ni]
+    ref = R.einsum_ref(a.detach().float(), b.detach().float())              # [nt, ni]
     assert float((out - ref).detach().abs().max()) < 2e-5
     once = (b.detach().float() @ a.detach().float()[k, 0]).unsqueeze(1)     # [nt, 1, n] -> the image with the token once
     want = once.sum(-1) / ((once != 0).float().sum(-1) + 1e-8)
@@ -124,7 +125,7 @@ def test_similarity_matrix_is_never_written():
     assert out.shape == (nt, ni)
     assert rise < s_bytes // 2, rise
     assert rise < 10e6, rise
-    ref = _einsum_ref(a.detach().float(), b.detach().float())
+    ref = R.einsum_ref(a.detach().float(), b.detach().float())
     assert float((out - ref).detach().abs().max()) < 2e-5
 
 
@@ -139,7 +140,7 @@ def test_score_fold_below_64_tokens(ni, q, nt, n, e, monkeypatch):
     """tests/test_late_interaction_gpu.py::test_fold_kernel_vs_reference_arithmetic below 64 tokens per image:
     `clipx_maxsim_score_fold` runs, 2e-5 against the einsum, and shrunk chunk limits (>= 2 text chunks; >= 2 image chunks where
     the image count has room for two alignment units) give bit-equal scores."""
-    ti, tt = _tokens(ni, q, nt, n, e)
+    ti, tt = R.tokens(ni, q, nt, n, e)
     a, b = ti.to(DEV).bfloat16(), tt.to(DEV).bfloat16()
     assert ops.maxsim_fused_applies(a, b)
     calls = []
@@ -148,15 +149,15 @@ def test_score_fold_below_64_tokens(ni, q, nt, n, e, monkeypatch):
     scores = ops.maxsim_scores(a, b, None, 0.0, 1.0)
     assert scores.shape == (ni, nt) and scores.dtype == torch.float32
     assert len(calls) == 1 and calls[0] == (nt, ni)
-    ref = _einsum_ref(a.float(), b.float())                     # [nt, ni]
+    ref = R.einsum_ref(a.float(), b.float())                     # [nt, ni]
     err = float((scores - ref.t()).abs().max())
     print(f"fold ({ni},{q},{nt},{n},{e}): max |scores - ref^T| = {err:.3e}")
     assert err < 2e-5, err
     cu, _ = ops.maxsim_pack_text(b)
     cu = cu.cpu().tolist()
     ci, rows = SCORE_SHRUNK[(ni, q, nt, n, e)]
-    _shrink(monkeypatch, ni, q, e, ci, rows)
-    image_chunks, text_chunks = ops.plan_maxsim_chunks(ni, q, e, cu, LS._MaxSimFused.CHUNK_BYTES)
+    R.shrink(monkeypatch, q, e, ci, rows)
+    image_chunks, text_chunks = ops.plan_maxsim_chunks(ni, q, e, cu, ops.MAXSIM_PARTIAL_BYTES)
     assert len(text_chunks) >= 2
     assert len(image_chunks) == (ni + ci - 1) // ci
     if (ni * q) % 8:
@@ -170,25 +171,20 @@ def test_score_fold_below_64_tokens(ni, q, nt, n, e, monkeypatch):
     assert float((ops.maxsim_scores(a, b, G, 0.3, 14.0) - want).abs().max()) < 14.0 * 2e-5
 
 
-Q49_MODEL = "ViT-q49-test-colxlip"
-Q49 = O.ClipCfg(embed_dim=128, image_size=112, patch_size=16, vision_width=128, vision_layers=2,
-                context_length=77, vocab_size=1024, text_width=128, text_heads=2, text_layers=2)
-
-
 def test_fused_route_through_a_49_token_model(monkeypatch):
     """ViT-q49-test-colxlip (112 px / patch 16: 49 image tokens, embed dim 128) in bf16: a training step through ColClipLoss and
     `get_logits` under no_grad both take the fused route.  The step against the oracle's `colxlip_loss_and_grads` with the bf16
     bounds of tests/test_model_gpu.py::test_colxlip_model_vs_oracle; the scores with the bounds of
     tests/test_late_interaction_gpu.py::test_fused_route_through_a_model."""
     from colxlip_amd.loss import ColClipLoss
-    sd = _colxlip_sd(Q49)
+    sd = R.model_state(Q49)
     image, text = O.synthetic_batch(Q49, 8, seed=21)
     ref_out, ref_res, ref_grads = O.colxlip_loss_and_grads(sd, image, text, Q49, alpha=0.4)
     gemms, folds = [], []
     gemm, fold = ops.maxsim_gemm, ops.maxsim_score_fold
     monkeypatch.setattr(ops, "maxsim_gemm", lambda *args: (gemms.append(args[2:4]), gemm(*args))[1])
     monkeypatch.setattr(ops, "maxsim_score_fold", lambda *args: (folds.append(args[:3]), fold(*args))[1])
-    model = _model(Q49_MODEL, sd, "bf16")
+    model = R.build_model(Q49_MODEL, sd, "bf16")
     model.train()
     model.zero_grad(set_to_none=True)
     out = model(image.to(DEV), text.to(DEV))

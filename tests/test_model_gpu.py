@@ -552,20 +552,20 @@ def test_colclip_loss_golden_fp32(golden_dir):
 
 def test_colclip_loss_bf16_chunked():
     """bf16 token features: MFMA NT/TN GEMM path, several text chunks, vs the fp32 path on the same (bf16-rounded) data."""
-    from colxlip_amd import loss as LS
+    from colxlip_amd import loss as LS, ops
     torch.manual_seed(3)
     n, nt, nq, e = 16, 77, 49, 64
     ti = torch.nn.functional.normalize(torch.randn(n, nq, e, device=DEV), dim=-1).bfloat16()
     tt = torch.nn.functional.normalize(torch.randn(n, nt, e, device=DEV), dim=-1).bfloat16()
     g = torch.randn(n, n, device=DEV)
-    old = LS._MaxSimLogits.CHUNK_BYTES
-    LS._MaxSimLogits.CHUNK_BYTES = 8 * nt * n * nq * 2           # 8 text samples per chunk -> 2 chunks
+    old = ops.MAXSIM_GENERAL_BYTES
+    ops.MAXSIM_GENERAL_BYTES = 8 * nt * n * nq * 2                # 8 text samples per chunk -> 2 chunks
     try:
         a, b = ti.clone().requires_grad_(True), tt.clone().requires_grad_(True)
         out = LS.compute_colbert_similarity(a, b)
         out.backward(g)
     finally:
-        LS._MaxSimLogits.CHUNK_BYTES = old
+        ops.MAXSIM_GENERAL_BYTES = old
     a32, b32 = ti.float().requires_grad_(True), tt.float().requires_grad_(True)
     ref = LS.compute_colbert_similarity(a32, b32)
     ref.backward(g)

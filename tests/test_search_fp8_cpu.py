@@ -12,27 +12,7 @@ import torch
 from colxlip_amd import _lib, ops
 from colxlip_amd import search as S
 from colxlip_amd.search import LateInteractionIndex
-
-
-def quant_model(x):
-    """`clipx_quant_rows_e4m3` in torch: frexp(amax) = fr * 2^ex; e = ex - 9 if fr <= 0.875 else ex - 8 (the smallest e with
-    amax * 2^-e <= 448), e = 0 for an all-zero row; bytes = float8_e4m3fn(ldexp(x, -e)).  x [..., E] -> (uint8 [..., E], int32 [...])"""
-    xf = x.float()
-    amax = xf.abs().amax(-1)
-    fr, ex = torch.frexp(amax)
-    e = torch.where(fr <= 0.875, ex - 9, ex - 8)
-    e = torch.where(amax > 0, e, torch.zeros_like(e)).to(torch.int32)
-    scaled = torch.ldexp(xf, -e.unsqueeze(-1))
-    return scaled.to(torch.float8_e4m3fn).view(torch.uint8), e
-
-
-def counts_model(txt):
-    """`clipx_maxsim_pack_text`'s cnt: the rows up to the last one that differs from the final row, plus one representative"""
-    nt, n, _ = txt.shape
-    bits = txt.view(torch.int16)
-    differs = (bits != bits[:, -1:, :]).any(-1)                                   # [nt, n]
-    last = torch.where(differs.any(1), (differs * torch.arange(n)).amax(1), torch.full((nt,), -1))
-    return (last + 2).to(torch.int32)
+from tests.late_interaction_ref import counts_model, quant_model
 
 
 def _rows(seed=0):

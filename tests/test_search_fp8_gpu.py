@@ -15,42 +15,17 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from colxlip_amd import create_model_and_transforms, ops  # noqa: E402
-from colxlip_amd import loss as LS  # noqa: E402
+from colxlip_amd import ops  # noqa: E402
 from colxlip_amd import search as S  # noqa: E402
 from colxlip_amd import train as TR  # noqa: E402
 from colxlip_amd.search import LateInteractionIndex, topk_reference  # noqa: E402
 from oracle import clip_oracle as O  # noqa: E402
+from tests import late_interaction_ref as LR  # noqa: E402
+from tests.late_interaction_ref import Q49  # noqa: E402
 
 DEV = "cuda"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INF = float("inf")
-
-
-def _tokens(ni, q, nt, n, e, distinct=False):
-    """Token features built like tests/test_late_interaction_gpu.py's: every position at / behind a per-sample EOT is one vector,
-    sample 1 has exact-zero rows there, sample 2 keeps distinct rows to the end, and the last sample's EOT is 0: one packed row.
-    `distinct`: every other sample keeps distinct rows too (many packed rows from few samples)."""
-    g = torch.Generator().manual_seed(100 + q)
-    ti = torch.nn.functional.normalize(torch.randn(ni, q, e, generator=g), dim=-1)
-    tt = torch.nn.functional.normalize(torch.randn(nt, n, e, generator=g), dim=-1)
-    tail = torch.nn.functional.normalize(torch.randn(e, generator=g), dim=-1)
-    for m in range(nt):
-        eot = 2 + (5 * m) % (n - 2)
-        if m == 1:
-            tt[m, eot:] = 0.0
-        elif m == nt - 1:
-            tt[m, :] = tail
-        elif m != 2 and not distinct:
-            tt[m, eot:] = tail
-    return ti.to(DEV).bfloat16(), tt.to(DEV).bfloat16()
-
-
-def _einsum_ref(ti, tt):
-    """reference loss.py:20-46 in the dtype of its arguments -> tok [nt, ni]"""
-    sim = torch.einsum('mnd,kqd->mknq', tt, ti)
-    mx = sim.max(dim=3)[0]
-    return mx.sum(-1) / ((mx != 0).to(mx.dtype).sum(-1) + 1e-8)
 
 
 def _dequantised(x):
@@ -88,7 +63,7 @@ def test_fp8_scorer_vs_reference_arithmetic(ni, q, nt, n, e, distinct, monkeypat
     Measured on an MI355X (max |scores - fp64|, fp8 route / bf16 route): (5,49,7,20,256) 1.21e-06 / 1.46e-08; (5,80,7,20,256)
     9.05e-07 / 1.74e-08; (9,16,6,9,256) 1.62e-06 / 1.39e-08; (7,64,24,20,256) 2.62e-06 / 1.82e-08.  Inside 2e-5, but the fp8 MFMA's
     sums are 50 to 150 times less accurate than the bf16 MFMA's."""
-    a, b = _tokens(ni, q, nt, n, e, distinct)
+    a, b = (t.to(DEV).bfloat16() for t in LR.tokens(ni, q, nt, n, e, distinct=distinct))
     assert ops.maxsim_fp8_applies(a, b)
     seen = _count_calls(monkeypatch, "maxsim_gemm_fp8", "maxsim_gemm", "maxsim_reduce")
     scores = ops.maxsim_scores_fp8(a, b, None, 0.0, 1.0)
@@ -99,7 +74,7 @@ def test_fp8_scorer_vs_reference_arithmetic(ni, q, nt, n, e, distinct, monkeypat
         assert R > 256 and ni * q > 256 and R % 256 and (ni * q) % 256          # several tiles each way, with tails
     da, db = _dequantised(a), _dequantised(b)
     assert torch.equal(da.bfloat16().float(), da) and torch.equal(db.bfloat16().float(), db)
-    ref = _einsum_ref(da.cpu().double(), db.cpu().double()).t()                  # [ni, nt] fp64
+    ref = LR.einsum_ref(da.cpu().double(), db.cpu().double()).t()                  # [ni, nt] fp64
     err8 = float((scores.cpu().double() - ref).abs().max())
     bf16 = ops.maxsim_scores(da.bfloat16(), db.bfloat16(), None, 0.0, 1.0)       # the fused bf16 route on the same values
     assert len(seen["maxsim_gemm"]) == 1
@@ -108,7 +83,7 @@ def test_fp8_scorer_vs_reference_arithmetic(ni, q, nt, n, e, distinct, monkeypat
           f"scores in {float(ref.min()):.3f} .. {float(ref.max()):.3f}, packed rows {R}")
     assert err8 <= max(4 * err16, 2e-5), (err8, err16)
     # how far the quantisation itself moves a score: reported, not bounded here
-    moved = float((scores.cpu().double() - _einsum_ref(a.cpu().double(), b.cpu().double()).t()).abs().max())
+    moved = float((scores.cpu().double() - LR.einsum_ref(a.cpu().double(), b.cpu().double()).t()).abs().max())
     print(f"    |fp8 scores - fp64 on the bf16 tokens| = {moved:.3e}")
 
 
@@ -116,18 +91,11 @@ def test_fp8_scorer_vs_reference_arithmetic(ni, q, nt, n, e, distinct, monkeypat
 SHRUNK = [(5, 80, 7, 20, 256, 2, 16), (9, 16, 6, 9, 256, 4, 16), (19, 49, 7, 20, 256, 8, 16)]
 
 
-def _shrink(monkeypatch, q, e, ci, rows):
-    """chunk limits under which the plan holds `ci` images of 1-byte elements per chunk and at most `rows` packed rows per text chunk"""
-    monkeypatch.setattr(ops, "MAXSIM_OPERAND_BYTES", ci * q * e)
-    monkeypatch.setattr(ops, "MAXSIM_TARGET_ROWS", rows)
-    monkeypatch.setattr(LS._MaxSimFused, "CHUNK_BYTES", ops.maxsim_partial_bytes(ci, q, rows))
-
-
 @pytest.mark.parametrize("ni,q,nt,n,e,ci,rows", SHRUNK)
 def test_either_side_stored_and_chunked(ni, q, nt, n, e, ci, rows, monkeypatch):
     """(bytes, exp) images and (bytes, exp, cnt) texts give the scores of the on-the-fly call bit for bit, alone and together; so
     does the plan shrunk to >= 2 image chunks and >= 2 text chunks."""
-    a, b = _tokens(ni, q, nt, n, e)
+    a, b = (t.to(DEV).bfloat16() for t in LR.tokens(ni, q, nt, n, e))
     G = torch.randn(ni, nt, generator=torch.Generator().manual_seed(5)).to(DEV)
     want = ops.maxsim_scores_fp8(a, b, G, 0.3, 14.0)
     img = ops.quant_tokens_e4m3(a)
@@ -138,8 +106,8 @@ def test_either_side_stored_and_chunked(ni, q, nt, n, e, ci, rows, monkeypatch):
     for i_side, t_side in ((img, b), (a, txt), (img, txt), (list(img), list(txt))):
         assert ops.maxsim_fp8_applies(i_side, t_side)
         assert torch.equal(_bits(ops.maxsim_scores_fp8(i_side, t_side, G, 0.3, 14.0)), _bits(want))
-    _shrink(monkeypatch, q, e, ci, rows)
-    image_chunks, text_chunks = ops.plan_maxsim_chunks(ni, q, e, cu.cpu().tolist(), LS._MaxSimFused.CHUNK_BYTES, elem_bytes=1)
+    LR.shrink(monkeypatch, q, e, ci, rows, elem_bytes=1)
+    image_chunks, text_chunks = ops.plan_maxsim_chunks(ni, q, e, cu.cpu().tolist(), ops.MAXSIM_PARTIAL_BYTES, elem_bytes=1)
     assert len(image_chunks) >= 2 and len(text_chunks) >= 2 and max(c for _, _, c in image_chunks) == ci
     if ni % ci:
         assert image_chunks[-1][1] - image_chunks[-1][0] < ci                                   # a shorter last chunk
@@ -154,7 +122,7 @@ def test_either_side_stored_and_chunked(ni, q, nt, n, e, ci, rows, monkeypatch):
 def test_fp8_combine_with_global_similarities():
     """scores = scale * (alpha * G + (1 - alpha) * tok^T) with random G; alpha = 1 is scale * G bit for bit, tokens unread."""
     ni, q, nt, n, e = 5, 80, 7, 20, 256
-    a, b = _tokens(ni, q, nt, n, e)
+    a, b = (t.to(DEV).bfloat16() for t in LR.tokens(ni, q, nt, n, e))
     G = torch.randn(ni, nt, generator=torch.Generator().manual_seed(5)).to(DEV)
     scale = 14.0
     tok_t = ops.maxsim_scores_fp8(a, b, None, 0.0, 1.0)
@@ -178,13 +146,13 @@ def test_fp8_fallback_route(ni, q, nt, n, e, env, monkeypatch):
     2e-5, from bf16 inputs and from the stored forms alike."""
     if env is not None:
         monkeypatch.setenv("CLIPX_MAXSIM_FUSED", env)
-    a, b = _tokens(ni, q, nt, n, e)
+    a, b = (t.to(DEV).bfloat16() for t in LR.tokens(ni, q, nt, n, e))
     assert not ops.maxsim_fp8_applies(a, b)
     monkeypatch.setattr(ops, "maxsim_gemm_fp8", lambda *args: pytest.fail("the fp8 GEMM ran"))
     seen = _count_calls(monkeypatch, "maxsim_reduce")
     scores = ops.maxsim_scores_fp8(a, b, None, 0.0, 1.0)
     assert scores.shape == (ni, nt) and len(seen["maxsim_reduce"]) >= 1
-    ref = _einsum_ref(_dequantised(a), _dequantised(b)).t()
+    ref = LR.einsum_ref(_dequantised(a), _dequantised(b)).t()
     err = float((scores - ref).abs().max())
     print(f"fp8 fallback ({ni},{q},{nt},{n},{e}, fused={env}): max error {err:.3e}")
     assert err < 2e-5, err
@@ -197,26 +165,6 @@ def test_fp8_fallback_route(ni, q, nt, n, e, env, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------ 2. the index
-def _features(n, e, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.nn.functional.normalize(torch.randn(n, e, generator=g), dim=-1)
-
-
-def _image_tokens(n, q, e, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.nn.functional.normalize(torch.randn(n, q, e, generator=g), dim=-1).bfloat16()
-
-
-def _text_tokens(n, length, e, seed):
-    """EOT-shaped: every position at and behind a per-sample EOT holds one vector"""
-    g = torch.Generator().manual_seed(seed)
-    t = torch.nn.functional.normalize(torch.randn(n, length, e, generator=g), dim=-1)
-    for m in range(n):
-        eot = 2 + (5 * m) % (length - 2)
-        t[m, eot:] = t[m, eot]
-    return t.bfloat16()
-
-
 @pytest.mark.parametrize("kind", ["image", "text"])
 def test_fp8_index_equals_dense_route(kind, monkeypatch):
     """The scheme of test_search_gpu.py::test_index_equals_dense_route: 35 = 2 * 16 + 3 gallery items in chunks of 16, 19 queries in
@@ -226,8 +174,8 @@ def test_fp8_index_equals_dense_route(kind, monkeypatch):
     monkeypatch.setattr(LateInteractionIndex, "CHUNK_ITEMS", 16)
     monkeypatch.setattr(LateInteractionIndex, "QUERY_CHUNK", 8)
     n_img, n_txt = (n_gal, n_qry) if kind == "image" else (n_qry, n_gal)
-    img_f, txt_f = _features(n_img, e, 1).to(DEV), _features(n_txt, e, 2).to(DEV)
-    img_t, txt_t = _image_tokens(n_img, q, e, 3).to(DEV), _text_tokens(n_txt, 20, e, 4).to(DEV)
+    img_f, txt_f = LR.features(n_img, e, 1).to(DEV), LR.features(n_txt, e, 2).to(DEV)
+    img_t, txt_t = LR.image_tokens(n_img, q, e, 3).to(DEV), LR.text_tokens(n_txt, 20, e, 4).to(DEV)
     gal_f, gal_t, qry_f, qry_t = (img_f, img_t, txt_f, txt_t) if kind == "image" else (txt_f, txt_t, img_f, img_t)
     ids = 1000 + 3 * torch.arange(n_gal)
     index = LateInteractionIndex(kind, alpha=alpha, scale=scale, device=DEV, token_dtype="fp8")
@@ -275,10 +223,10 @@ def test_fp8_index_save_load_search_and_size(kind, tmp_path, monkeypatch):
     monkeypatch.setattr(LateInteractionIndex, "IO_ITEMS", 7)
     e = 256
     if kind == "image":
-        gal_t, qt = _image_tokens(35, 49, e, 3).to(DEV), _text_tokens(19, 20, e, 4).to(DEV)
+        gal_t, qt = LR.image_tokens(35, 49, e, 3).to(DEV), LR.text_tokens(19, 20, e, 4).to(DEV)
     else:
-        gal_t, qt = _text_tokens(35, 20, e, 3).to(DEV), _image_tokens(19, 49, e, 4).to(DEV)
-    gal_f, qf = _features(35, e, 1).to(DEV), _features(19, e, 2).to(DEV)
+        gal_t, qt = LR.text_tokens(35, 20, e, 3).to(DEV), LR.image_tokens(19, 49, e, 4).to(DEV)
+    gal_f, qf = LR.features(35, e, 1).to(DEV), LR.features(19, e, 2).to(DEV)
     ids = torch.arange(35) * 2 + 5
     index = LateInteractionIndex(kind, alpha=0.4, scale=20.0, device=DEV, token_dtype="fp8").add(gal_f, gal_t, ids=ids)
     plain = LateInteractionIndex(kind, alpha=0.4, scale=20.0, device=DEV).add(gal_f, gal_t, ids=ids)
@@ -311,11 +259,11 @@ def test_fp8_peak_memory_does_not_grow_with_the_gallery(monkeypatch):
     `search` allocates above what is live before it is the same, within 64 KiB, for 2 048 and 4 096 gallery items."""
     monkeypatch.setattr(LateInteractionIndex, "CHUNK_ITEMS", 256)
     e = 256
-    qf, qt = _features(64, e, 2).to(DEV), _text_tokens(64, 20, e, 4).to(DEV)
+    qf, qt = LR.features(64, e, 2).to(DEV), LR.text_tokens(64, 20, e, 4).to(DEV)
     peaks = []
     for n in (2048, 4096):
         index = LateInteractionIndex("image", alpha=0.5, scale=10.0, device=DEV, token_dtype="fp8")
-        index.add(_features(n, e, 1).to(DEV), _image_tokens(n, 16, e, 3).to(DEV))
+        index.add(LR.features(n, e, 1).to(DEV), LR.image_tokens(n, 16, e, 3).to(DEV))
         assert index.token_bytes() == n * 16 * (e + 4)
         index.search(qf, qt, 10)                                   # warm: library handles, kernel attributes
         torch.cuda.synchronize()
@@ -332,16 +280,10 @@ def test_fp8_peak_memory_does_not_grow_with_the_gallery(monkeypatch):
 
 # ------------------------------------------------------------------------------------------------ 3. through a model and the CLI
 NAME = "ViT-q49-test-colxlip"            # embed dim 128: below the kernel's 256, so the plumbing is checked on the fallback route
-Q49 = O.ClipCfg(embed_dim=128, image_size=112, patch_size=16, vision_width=128, vision_layers=2,
-                context_length=77, vocab_size=1024, text_width=128, text_heads=2, text_layers=2)
 
 
 def _model():
-    sd = O.perturb_state_dict(O.init_state_dict(Q49, seed=3), seed=4)
-    sd.update(O.perturb_state_dict(O.init_colxlip_heads(Q49, seed=5), seed=6))
-    model, _, _ = create_model_and_transforms(NAME, precision="bf16", device=DEV, output_dict=True)
-    model.load_state_dict({k: v.clone() for k, v in sd.items()}, strict=True)
-    return model.eval()
+    return LR.build_model(NAME, LR.model_state(Q49), "bf16").eval()
 
 
 def test_fp8_search_through_a_model(monkeypatch):
@@ -374,11 +316,6 @@ def test_fp8_search_through_a_model(monkeypatch):
         images.search_images(model, image, 3)
 
 
-_LAUNCHER = ("import os, sys; sys.path.insert(0, sys.argv[1]); from colxlip_amd import add_model_config; "
-             "add_model_config(os.path.join(sys.argv[1], 'tests', 'model_configs')); from colxlip_amd.search import main; "
-             "sys.exit(main(sys.argv[2:]))")
-
-
 def test_fp8_cli_save_then_load(tmp_path):
     """python -m colxlip_amd.search --index-dtype fp8 --save-index, then --load-index (which takes the dtype from meta.json):
     identical results.npz, and the directory holds the fp8 files."""
@@ -387,7 +324,7 @@ def test_fp8_cli_save_then_load(tmp_path):
     torch.save({"state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}}, ckpt)
     del model
     index_dir = str(tmp_path / "index")
-    base = [sys.executable, *(["-s"] if sys.flags.no_user_site else []), "-c", _LAUNCHER, ROOT, "--model", NAME, "--dataset-type",
+    base = [sys.executable, *(["-s"] if sys.flags.no_user_site else []), "-c", LR.LAUNCHER, ROOT, "--model", NAME, "--dataset-type",
             "synthetic", "--precision", "bf16", "--batch-size", "16", "--retrieval-coco", "--val-num-samples", "16", "--alpha", "0.5",
             "--pretrained", ckpt, "--direction", "t2i", "--k", "5"]
     outs = []

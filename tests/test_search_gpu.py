@@ -12,12 +12,14 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from colxlip_amd import create_model_and_transforms, ops  # noqa: E402
+from colxlip_amd import ops  # noqa: E402
 from colxlip_amd import search as S  # noqa: E402
 from colxlip_amd import train as TR  # noqa: E402
 from colxlip_amd.data import get_data  # noqa: E402
 from colxlip_amd.search import LateInteractionIndex, topk_reference  # noqa: E402
 from oracle import clip_oracle as O  # noqa: E402
+from tests import late_interaction_ref as R  # noqa: E402
+from tests.late_interaction_ref import Q49  # noqa: E402
 
 DEV = "cuda"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -152,26 +154,6 @@ def test_refusals_launch_nothing():
 
 
 # ------------------------------------------------------------------------------------------------ 4. index vs the dense route
-def _features(n, e, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.nn.functional.normalize(torch.randn(n, e, generator=g), dim=-1)
-
-
-def _image_tokens(n, q, e, dtype, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.nn.functional.normalize(torch.randn(n, q, e, generator=g), dim=-1).to(dtype)
-
-
-def _text_tokens(n, length, e, dtype, seed):
-    """EOT-shaped: every position at and behind a per-sample EOT holds one vector"""
-    g = torch.Generator().manual_seed(seed)
-    t = torch.nn.functional.normalize(torch.randn(n, length, e, generator=g), dim=-1)
-    for m in range(n):
-        eot = 2 + (5 * m) % (length - 2)
-        t[m, eot:] = t[m, eot]
-    return t.to(dtype)
-
-
 ROUTES = {"fused_bf16": (49, 128, torch.bfloat16, 0.4), "general_fp32": (16, 64, torch.float32, 0.4), "global_only": (49, 128, None, 1.0)}
 
 
@@ -186,9 +168,9 @@ def test_index_equals_dense_route(kind, route, monkeypatch):
     monkeypatch.setattr(LateInteractionIndex, "CHUNK_ITEMS", 16)
     monkeypatch.setattr(LateInteractionIndex, "QUERY_CHUNK", 8)
     n_img, n_txt = (n_gal, n_qry) if kind == "image" else (n_qry, n_gal)
-    img_f, txt_f = _features(n_img, e, 1).to(DEV), _features(n_txt, e, 2).to(DEV)
-    img_t = None if dtype is None else _image_tokens(n_img, q, e, dtype, 3).to(DEV)
-    txt_t = None if dtype is None else _text_tokens(n_txt, 20, e, dtype, 4).to(DEV)
+    img_f, txt_f = R.features(n_img, e, 1).to(DEV), R.features(n_txt, e, 2).to(DEV)
+    img_t = None if dtype is None else R.image_tokens(n_img, q, e, 3, dtype).to(DEV)
+    txt_t = None if dtype is None else R.text_tokens(n_txt, 20, e, 4, dtype).to(DEV)
     gal_f, gal_t, qry_f, qry_t = (img_f, img_t, txt_f, txt_t) if kind == "image" else (txt_f, txt_t, img_f, img_t)
     ids = 1000 + 3 * torch.arange(n_gal)
     routes_taken = []
@@ -262,8 +244,6 @@ def test_orderings_equal_reference_fixture(golden_dir):
 # ------------------------------------------------------------------------------------------------ 6. through a model
 SMALL = O.ClipCfg(embed_dim=64, image_size=64, patch_size=16, vision_width=128, vision_layers=2,
                   context_length=77, vocab_size=1024, text_width=128, text_heads=2, text_layers=2)
-Q49 = O.ClipCfg(embed_dim=128, image_size=112, patch_size=16, vision_width=128, vision_layers=2,
-                context_length=77, vocab_size=1024, text_width=128, text_heads=2, text_layers=2)
 TINY = O.ClipCfg(embed_dim=32, image_size=32, patch_size=16, vision_width=64, vision_layers=2,
                  context_length=77, vocab_size=512, text_width=64, text_heads=2, text_layers=2)
 MODELS = {"ViT-q49-test-colxlip": (Q49, "bf16"), "ViT-small-test-colxlip": (SMALL, "fp32"), "ViT-tiny-test": (TINY, "fp32")}
@@ -271,12 +251,7 @@ MODELS = {"ViT-q49-test-colxlip": (Q49, "bf16"), "ViT-small-test-colxlip": (SMAL
 
 def _model(name):
     cfg, precision = MODELS[name]
-    sd = O.perturb_state_dict(O.init_state_dict(cfg, seed=3), seed=4)
-    if "colxlip" in name:
-        sd.update(O.perturb_state_dict(O.init_colxlip_heads(cfg, seed=5), seed=6))
-    model, _, _ = create_model_and_transforms(name, precision=precision, device=DEV, output_dict=True)
-    model.load_state_dict({k: v.clone() for k, v in sd.items()}, strict=True)
-    return model.eval(), cfg, precision
+    return R.build_model(name, R.model_state(cfg, heads="colxlip" in name), precision).eval(), cfg, precision
 
 
 @pytest.mark.parametrize("name", list(MODELS))
@@ -311,8 +286,8 @@ def test_loaded_index_returns_identical_results(tmp_path, monkeypatch):
     monkeypatch.setattr(LateInteractionIndex, "CHUNK_ITEMS", 16)
     monkeypatch.setattr(LateInteractionIndex, "IO_ITEMS", 7)
     index = LateInteractionIndex("image", alpha=0.4, scale=20.0, device=DEV)
-    index.add(_features(35, 128, 1).to(DEV), _image_tokens(35, 49, 128, torch.bfloat16, 3).to(DEV), ids=torch.arange(35) * 2 + 5)
-    qf, qt = _features(19, 128, 2).to(DEV), _text_tokens(19, 20, 128, torch.bfloat16, 4).to(DEV)
+    index.add(R.features(35, 128, 1).to(DEV), R.image_tokens(35, 49, 128, 3, torch.bfloat16).to(DEV), ids=torch.arange(35) * 2 + 5)
+    qf, qt = R.features(19, 128, 2).to(DEV), R.text_tokens(19, 20, 128, 4, torch.bfloat16).to(DEV)
     first = index.search(qf, qt, 10)
     back = LateInteractionIndex.load(index.save(str(tmp_path / "idx")), device=DEV)
     assert len(back) == 35 and [c[1].shape[0] for c in back.chunks()] == [16, 16, 3] and back.chunks()[0][1].is_cuda
@@ -330,13 +305,13 @@ def test_peak_memory_does_not_grow_with_the_gallery(route, monkeypatch):
     monkeypatch.setattr(LateInteractionIndex, "CHUNK_ITEMS", 256)
     e = 128
     if route == "global":
-        qf, qt = _features(512, e, 2).to(DEV), None
+        qf, qt = R.features(512, e, 2).to(DEV), None
     else:
-        qf, qt = _features(64, e, 2).to(DEV), _text_tokens(64, 20, e, torch.bfloat16, 4).to(DEV)
+        qf, qt = R.features(64, e, 2).to(DEV), R.text_tokens(64, 20, e, 4, torch.bfloat16).to(DEV)
     peaks = []
     for n in (2048, 4096):
         index = LateInteractionIndex("image", alpha=1.0 if route == "global" else 0.5, scale=10.0, device=DEV)
-        index.add(_features(n, e, 1).to(DEV), None if route == "global" else _image_tokens(n, 16, e, torch.bfloat16, 3).to(DEV))
+        index.add(R.features(n, e, 1).to(DEV), None if route == "global" else R.image_tokens(n, 16, e, 3, torch.bfloat16).to(DEV))
         index.search(qf, qt, 10)                                   # warm: library handles, kernel attributes
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
@@ -353,11 +328,6 @@ def test_peak_memory_does_not_grow_with_the_gallery(route, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------ 9. command line
-_LAUNCHER = ("import os, sys; sys.path.insert(0, sys.argv[1]); from colxlip_amd import add_model_config; "
-             "add_model_config(os.path.join(sys.argv[1], 'tests', 'model_configs')); from colxlip_amd.search import main; "
-             "sys.exit(main(sys.argv[2:]))")
-
-
 @pytest.fixture(scope="module")
 def cli_case(tmp_path_factory):
     """ViT-small-test-colxlip (fp32) on a synthetic retrieval split of 64 images x 5 captions: evaluate()'s metrics, the dense
@@ -390,7 +360,7 @@ def test_cli_recalls_equal_evaluate(cli_case, direction):
         assert bool((top[:, K - 1] > top[:, K]).all()), f"an exact tie straddles rank {K}: R@{K} is ambiguous"
     out = str(c["tmp"] / f"{direction}.npz")
     index_dir = str(c["tmp"] / f"index_{direction}")
-    cmd = [sys.executable, *(["-s"] if sys.flags.no_user_site else []), "-c", _LAUNCHER, ROOT, *c["argv"], "--pretrained", c["ckpt"],
+    cmd = [sys.executable, *(["-s"] if sys.flags.no_user_site else []), "-c", R.LAUNCHER, ROOT, *c["argv"], "--pretrained", c["ckpt"],
            "--direction", direction, "--k", "10", "--out", out, "--save-index", index_dir]
     done = subprocess.run(cmd, cwd=str(c["tmp"]), capture_output=True, text=True, timeout=300)
     assert done.returncode == 0, done.stderr[-2000:]
