@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libclipx_hip.so")
-SOURCES = ["elementwise.hip", "gemm_f32.hip", "gemm_bf16_nt.hip", "gemm_bf16_nt5.hip", "gemm_bf16_nt8p.hip", "gemm_fp8_nt8p.hip", "gemm_bf16_tn.hip", "linear.hip", "attention.hip", "attention_pooled.hip", "colbert.hip", "topk.hip", "loss_fused.hip", "loss_sigmoid.hip", "loss_distill.hip", "patch_dropout.hip", "image_transform.hip"]
+SOURCES = ["elementwise.hip", "gemm_f32.hip", "gemm_bf16_nt.hip", "gemm_bf16_nt5.hip", "gemm_bf16_nt8p.hip", "gemm_fp8_nt8p.hip", "gemm_bf16_tn.hip", "linear.hip", "attention.hip", "attention_pooled.hip", "colbert.hip", "maxsim_pairs.hip", "topk.hip", "loss_fused.hip", "loss_sigmoid.hip", "loss_distill.hip", "patch_dropout.hip", "image_transform.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result"] + os.environ.get("CLIPX_EXTRA_FLAGS", "").split()
 
 

@@ -1276,6 +1276,140 @@ def maxsim_scores_fp8(img, txt, G, alpha, scale, out=None):
         return _maxsim_scores_general(dequant_tokens_e4m3(ti, ie), dequant_tokens_e4m3(tt, te), G, alpha, scale, out)
 
 
+# ------------------------------------------------------------------ gathered MaxSim (late-interaction reranking)
+MAXSIM_PAIRS_ROWS = 80                   # query rows `clipx_maxsim_pairs` stages: five 16-row tiles of accumulators (MSP_QT)
+MAXSIM_PAIRS_STAGE_BYTES = 128 << 10     # ... and their bytes in LDS, rows padded to 16 and to e + 8 elements (MSP_LDS_BYTES)
+
+
+def maxsim_pairs_takes(q: int, n: int, e: int, gallery_is_image=None) -> bool:
+    """Whether `clipx_maxsim_pairs` (csrc/maxsim_pairs.hip) scores pairs of images of `q` and texts of `n` tokens of `e` bf16
+    elements.  The rule of the bf16 fused route, e % 64 == 0, e >= 128 and q >= 16 (the kernel walks a row in 32-element MFMA steps
+    and masks, not skips, a partial 16-row tile), and the kernel's own limit: the QUERY side is staged whole in LDS and held in five
+    16-row accumulator tiles, so it has at most 80 rows and 16-padded rows x (e + 8) x 2 bytes <= 128 KiB.  The query side is the
+    text (n rows) over an image gallery and the image (q rows) over a text gallery; `gallery_is_image=None` asks for both
+    directions.  The gallery side streams and has no limit."""
+    if not (e % 64 == 0 and e >= 128 and q >= 16 and n >= 1):
+        return False
+    sides = {True: (n,), False: (q,), None: (q, n)}[gallery_is_image]
+    return all(r <= MAXSIM_PAIRS_ROWS and (r + 15) // 16 * 16 * (e + 8) * 2 <= MAXSIM_PAIRS_STAGE_BYTES for r in sides)
+
+
+def _pair_chunks(gallery_chunks):
+    """[tokens or (tokens, cnt or None)] -> ([tokens], [cnt or None])"""
+    toks, cnts = [], []
+    for c in gallery_chunks:
+        t, cnt = (c[0], c[1] if len(c) > 1 else None) if isinstance(c, (tuple, list)) else (c, None)
+        toks.append(t)
+        cnts.append(cnt)
+    return toks, cnts
+
+
+def _maxsim_pairs_general(query_tokens, toks, chunk_items, cand, Gp, alpha, scale, gallery_is_image, out):
+    """The plain route of `maxsim_pair_scores`: torch on the device in fp32, over query chunks whose gathered tokens and
+    similarities stay within MAXSIM_GENERAL_BYTES: gather, einsum, max, masked mean over all n text rows (the rows of a
+    bitwise-equal tail have equal maxima, so this is the weighted mean of the packed rows up to summation order)."""
+    nq, C = cand.shape
+    rows_g, e = toks[0].shape[1], toks[0].shape[2]
+    rows_q = query_tokens.shape[1]
+    per_query = 4 * C * (rows_g * e + 2 * rows_g * rows_q)
+    step = max(1, min(nq, MAXSIM_GENERAL_BYTES // max(1, per_query)))
+    for a in range(0, nq, step):
+        b = min(nq, a + step)
+        pos = cand[a:b].long()
+        live = pos >= 0
+        p = pos.clamp(min=0)
+        g = torch.zeros((b - a, C, rows_g, e), dtype=torch.float32, device=cand.device)
+        for ci, t in enumerate(toks):
+            m = live & (p // chunk_items == ci)
+            g[m] = t[(p[m] - ci * chunk_items)].float()
+        qt = query_tokens[a:b].float()
+        if gallery_is_image:
+            sim = torch.einsum("mnd,mcqd->mcnq", qt, g)
+        else:
+            sim = torch.einsum("mcnd,mqd->mcnq", g, qt)
+        mx = sim.max(dim=3)[0]
+        del sim, g
+        tok = mx.sum(-1) / ((mx != 0).to(torch.float32).sum(-1) + 1e-8)
+        blk = (1.0 - alpha) * tok
+        if Gp is not None:
+            blk = alpha * Gp[a:b] + blk
+        out[a:b] = torch.where(live, scale * blk, torch.full_like(blk, float("-inf")))
+    return out
+
+
+def maxsim_pair_scores(query_tokens, gallery_chunks, chunk_items, cand, Gp, alpha, scale, gallery_is_image, out=None):
+    """Late-interaction scores of chosen (query, gallery item) pairs: out [nq, C] fp32,
+        out[i, c] = scale * (alpha * Gp[i, c] + (1 - alpha) * MaxSim(pair i, cand[i, c])),     -inf where cand[i, c] == -1
+    with MaxSim as in `maxsim_scores`.  query_tokens [nq, rows, e] is one tensor; the gallery is its chunked storage as it is:
+    `gallery_chunks` lists the token tensors [items, rows, e] (the last one may hold fewer than `chunk_items` items), for a bf16
+    text gallery (tokens, cnt) with cnt = `maxsim_text_counts` of the chunk (computed here when missing); position p is item
+    p % chunk_items of chunk p // chunk_items.  gallery_is_image: the queries are texts and the gallery holds images, else the
+    other way round.  cand [nq, C] int, contiguous; Gp [nq, C] fp32 global similarities of the pairs or None (no global term).
+    bf16 tokens of a shape `maxsim_pairs_takes` go through `clipx_maxsim_pairs`: nothing is gathered or packed.  Everything
+    else -- fp32 tokens, other shapes, CLIPX_MAXSIM_FUSED=0 -- takes the plain torch route in fp32: the same numbers up to
+    summation order.  alpha = 1 is scale * Gp (bit for bit) and reads no tokens."""
+    alpha, scale = float(alpha), float(scale)
+    if cand.dim() != 2 or cand.dtype not in (torch.int32, torch.int64):
+        raise ValueError("maxsim_pair_scores: cand must be [nq, C] int32 or int64")
+    nq, C = cand.shape
+    if (C > 1 and cand.stride(1) != 1) or (nq > 1 and cand.stride(0) != C):
+        raise ValueError(f"maxsim_pair_scores: cand must be contiguous (strides {tuple(cand.stride())} for shape {(nq, C)})")
+    dev = cand.device
+    if Gp is not None:
+        if Gp.shape != (nq, C) or Gp.dtype != torch.float32 or (C > 1 and Gp.stride(1) != 1):
+            raise ValueError("maxsim_pair_scores: Gp must be [nq, C] fp32 with a unit column stride")
+    if out is None:
+        out = torch.empty((nq, C), dtype=torch.float32, device=dev)
+    if out.shape != (nq, C) or out.dtype != torch.float32 or (C > 1 and out.stride(1) != 1):
+        raise ValueError("maxsim_pair_scores: out must be [nq, C] fp32 with a unit column stride")
+    if nq == 0 or C == 0:
+        return out
+    with torch.no_grad():
+        if alpha == 1.0:
+            if Gp is None:
+                raise ValueError("maxsim_pair_scores: alpha = 1 scores with the global similarities only and needs Gp")
+            torch.mul(Gp, scale, out=out)
+            out.masked_fill_(cand < 0, float("-inf"))
+            return out
+        toks, cnts = _pair_chunks(gallery_chunks)
+        n_items = (len(toks) - 1) * int(chunk_items) + toks[-1].shape[0] if toks else 0
+        if any(t.shape[0] != chunk_items for t in toks[:-1]) or (toks and not 1 <= toks[-1].shape[0] <= chunk_items):
+            raise ValueError("maxsim_pair_scores: every chunk but the last holds chunk_items items")
+        if not toks:
+            if bool((cand != -1).any()):
+                raise ValueError("maxsim_pair_scores: a candidate position in an empty gallery")
+            return out.fill_(float("-inf"))
+        query_tokens = query_tokens.detach()
+        q, n = (toks[0].shape[1], query_tokens.shape[1]) if gallery_is_image else (query_tokens.shape[1], toks[0].shape[1])
+        e = query_tokens.shape[2]
+        if query_tokens.shape[0] != nq or any(t.shape[1:] != toks[0].shape[1:] or t.dtype != query_tokens.dtype for t in toks) \
+                or toks[0].shape[2] != e:
+            raise ValueError("maxsim_pair_scores: token shapes or dtypes of the query and the gallery chunks disagree")
+        fused = (query_tokens.dtype == torch.bfloat16 and query_tokens.is_cuda and maxsim_pairs_takes(q, n, e, bool(gallery_is_image))
+                 and os.environ.get("CLIPX_MAXSIM_FUSED", "1") != "0")
+        if not fused:
+            if bool(((cand < -1) | (cand >= n_items)).any()):
+                raise ValueError(f"maxsim_pair_scores: a candidate position lies outside [0, {n_items}) and is not -1")
+            return _maxsim_pairs_general(query_tokens, toks, int(chunk_items), cand, Gp, alpha, scale, bool(gallery_is_image), out)
+        query_tokens = query_tokens.contiguous()
+        cand32 = cand if cand.dtype == torch.int32 else cand.to(torch.int32)
+        query_cnt = gal_cnt = None
+        if gallery_is_image:
+            query_cnt = maxsim_text_counts(query_tokens)
+        else:
+            cnts = [c if c is not None else maxsim_text_counts(t.contiguous()) for t, c in zip(toks, cnts)]
+            assert all(c.dtype == torch.int32 and c.is_contiguous() and c.shape[0] >= t.shape[0] for t, c in zip(toks, cnts))
+            gal_cnt = torch.tensor([c.data_ptr() for c in cnts], dtype=torch.int64, device=dev)
+        gal_tok = torch.tensor([_p(_c(t)) for t in toks], dtype=torch.int64, device=dev)
+        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        ld = (lambda t: t.stride(0)) if nq > 1 else (lambda t: C)        # the stride of a dimension of one element says nothing
+        check(_lib.lib().clipx_maxsim_pairs(1 if gallery_is_image else 0, nq, C, q, n, e, _p(query_tokens), _p(query_cnt), _p(gal_tok),
+                                            _p(gal_cnt), len(toks), int(chunk_items), n_items, _p(cand32), C, _p(Gp),
+                                            0 if Gp is None else ld(Gp), _p(out), ld(out), alpha, float(1.0 - alpha),
+                                            scale, _p(status), _stream()))
+        return out
+
+
 # ------------------------------------------------------------------ streaming top-k (late-interaction search)
 TOPK_MAX_K = 256
 

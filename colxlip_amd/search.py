@@ -8,7 +8,7 @@ arithmetic); the selection replaces the reference's per-row CPU argsort (train.p
 
     python -m colxlip_amd.search --model NAME [--pretrained CKPT] [--precision bf16] --dataset-type synthetic|packed
         [--val-data DIR] --retrieval-coco --direction t2i|i2t --k 10 --out results.npz [--save-index DIR | --load-index DIR]
-        [--index-dtype model|fp8]
+        [--index-dtype model|fp8] [--candidates C]
 
 `token_dtype="fp8"` keeps the gallery's token features as e4m3 bytes with one power-of-two exponent per token
 (`ops.quant_tokens_e4m3`): half the bytes of bf16 plus 4 per token, scored by `ops.maxsim_scores_fp8` on the fp8 MFMA.
@@ -104,6 +104,7 @@ class LateInteractionIndex:
         self.device = torch.device(device)
         self._feat, self._tok = [], []           # chunks [chunk, E] fp32 / [chunk, q, E]; the last one may be partly filled
         self._tok_exp, self._tok_cnt = [], []    # fp8: chunks [chunk, q] int32 / (text gallery) [chunk] int32 beside the bytes in _tok
+        self._pair_cnt = {}                      # bf16 text gallery, rerank: chunk number -> cnt [items] int32 (ops.maxsim_text_counts)
         self._ids = torch.empty((0,), dtype=torch.int64, device=self.device)      # capacity doubles
         self._n = 0
         self._chunk = None                       # items per chunk, fixed by the first add
@@ -190,6 +191,7 @@ class LateInteractionIndex:
                 self._tok[-1][fill:want] = tokens[done:done + take].detach().to(self.device)
             for x, store in zip(extra, (self._tok_exp, self._tok_cnt)):
                 store[-1][fill:want] = x[done:done + take].to(self.device)
+            self._pair_cnt.pop(len(self._feat) - 1, None)        # the chunk changed: its counts are recomputed when next needed
             done += take
             self._n += take
         return self
@@ -239,12 +241,18 @@ class LateInteractionIndex:
         return sum(t.numel() * t.element_size() for store in (self._tok, self._tok_exp, self._tok_cnt) for t in store)
 
     # ------------------------------------------------------------------ search
-    def search(self, features, tokens, k):
+    def search(self, features, tokens, k, candidates=None):
         """features [nq, E] fp32 (normalised), tokens [nq, n, E] or None (alpha = 1) of the OTHER side -> (scores [nq, k] fp32,
         ids [nq, k] int64) on the device, best first (larger score, then earlier gallery position); slots beyond the gallery
         size hold (-inf, -1).  Nothing of size gallery x queries is allocated.  An fp8 index quantises the query tokens once per
         query chunk (fp32 ones are cast to bf16 first) and scores with `ops.maxsim_scores_fp8`; no bf16 copy of a gallery chunk
-        is made."""
+        is made.
+        `candidates=C` (k <= C <= ops.TOPK_MAX_K) searches in two stages: the C best gallery items per query by the GLOBAL
+        similarity alone (the same loop with `similarity_matrix` merged directly, no token kernel), then `rerank` of those
+        positions with the full score, reusing the first stage's global similarities.  The result is the exact top k of the
+        candidates, not of the gallery; with C >= len(self) it is the exhaustive result up to summation order."""
+        if candidates is not None and candidates != 0:
+            return self._search_two_stage(features, tokens, k, int(candidates))
         nq = features.shape[0]
         dev = self.device
         if self.alpha == 1.0:
@@ -286,6 +294,123 @@ class LateInteractionIndex:
         found = self._ids[:self._n][pos.clamp_(min=0)]
         return best_val, torch.where(best_idx >= 0, found, torch.full_like(found, -1))
 
+    # ------------------------------------------------------------------ two-stage search and reranking
+    def _refuse_rerank(self, what):
+        if self.alpha == 1.0 or self.prescale:
+            raise ValueError(f"LateInteractionIndex.{what}: alpha = 1 (or prescale) scores with the global features alone; the exact "
+                             "search is already the global one, there is nothing to rerank")
+        if self.token_dtype == "fp8":
+            raise ValueError(f"LateInteractionIndex.{what}: an fp8 token index is not reranked (the gathered MaxSim kernel reads bf16 "
+                             "tokens; dequantising the gallery is not done silently)")
+
+    def _pair_chunks(self):
+        """the token storage as `ops.maxsim_pair_scores` takes it: the chunks' filled parts, a bf16 text gallery's with their cnt"""
+        out = []
+        for c, (base, _, tok) in enumerate(self.chunks()):
+            if self.kind == "text" and tok.dtype == torch.bfloat16:
+                cnt = self._pair_cnt.get(c)
+                if cnt is None or cnt.shape[0] != tok.shape[0]:
+                    cnt = self._pair_cnt[c] = ops.maxsim_text_counts(tok)
+                out.append((tok, cnt))
+            else:
+                out.append(tok)
+        return out
+
+    def _pair_globals(self, qf, pos):
+        """fp32 global similarities of the pairs (qf [m, E], pos [m, C] int64, -1 = empty): [m, C], 0 at empty slots; the gallery
+        features are gathered chunk by chunk, 64 MiB of them at a time"""
+        m, C = pos.shape
+        e = qf.shape[1]
+        out = torch.zeros((m, C), dtype=torch.float32, device=self.device)
+        step = max(1, (64 << 20) // max(1, 4 * C * e))
+        for a in range(0, m, step):
+            p = pos[a:a + step]
+            rows = torch.arange(a, a + p.shape[0], device=self.device).unsqueeze(1).expand_as(p)
+            for base, gf, _ in self.chunks():
+                hit = (p >= base) & (p < base + gf.shape[0])
+                out[a:a + step][hit] = (gf[p[hit] - base] * qf[rows[hit]]).sum(-1)
+        return out
+
+    def rerank(self, features, tokens, positions, k=None, global_scores=None):
+        """The full scores of chosen candidates: features [nq, E] fp32 and tokens [nq, n, E] of the queries, positions [nq, C] int
+        (gallery POSITIONS, -1 = an empty slot; duplicates are scored as given).  k None -> scores [nq, C] fp32 in the given slot
+        order, -inf at empty slots.  With k -> (scores [nq, k], ids [nq, k] int64) best first under the index's order (larger
+        score, then smaller gallery position), positions mapped through `ids` as `search` does, (-inf, -1) behind the last
+        candidate.  The global term comes from the fp32 features of the pairs, or from `global_scores` [nq, C] fp32 when the
+        caller has them (`search(candidates=C)` passes its first stage's).  Scoring is `ops.maxsim_pair_scores` per query chunk."""
+        self._refuse_rerank("rerank")
+        if tokens is None or not self._tok and self._n:
+            raise ValueError("LateInteractionIndex.rerank: needs token features on both sides")
+        positions = torch.as_tensor(positions)
+        if positions.dim() != 2 or positions.shape[0] != features.shape[0] or positions.dtype not in (torch.int32, torch.int64):
+            raise ValueError("LateInteractionIndex.rerank: positions must be [nq, C] int32 or int64")
+        nq, C = positions.shape
+        if (C > 1 and positions.stride(1) != 1) or (nq > 1 and positions.stride(0) != C):
+            raise ValueError("LateInteractionIndex.rerank: positions must be contiguous")
+        if k is not None and not 1 <= k <= ops.TOPK_MAX_K:
+            raise ValueError(f"LateInteractionIndex.rerank: k must be in 1 .. {ops.TOPK_MAX_K} (got {k})")
+        dev = self.device
+        positions = positions.to(dev)
+        if positions.numel() and (int(positions.max()) >= self._n or int(positions.min()) < -1):
+            raise ValueError(f"LateInteractionIndex.rerank: a position lies outside [0, {self._n}) and is not -1")
+        if global_scores is not None and (global_scores.shape != positions.shape or global_scores.dtype != torch.float32):
+            raise ValueError("LateInteractionIndex.rerank: global_scores must be [nq, C] fp32")
+        features = features.detach().to(dev).float().contiguous()
+        tokens = tokens.detach().to(dev)
+        scores = torch.empty((nq, C), dtype=torch.float32, device=dev)
+        gallery_is_image = self.kind == "image"
+        qchunk = max(1, int(self.QUERY_CHUNK))
+        with torch.no_grad():
+            chunks = self._pair_chunks()
+            for q0 in range(0, nq, qchunk):
+                q1 = min(nq, q0 + qchunk)
+                pos = positions[q0:q1]
+                Gp = global_scores[q0:q1].to(dev) if global_scores is not None else self._pair_globals(features[q0:q1], pos.long())
+                ops.maxsim_pair_scores(tokens[q0:q1], chunks, self._chunk, pos, Gp, self.alpha, self.scale, gallery_is_image,
+                                       out=scores[q0:q1])
+            if k is None:
+                return scores
+            best_val, best_idx = ops.topk_init(nq, k, dev)
+            if nq == 0 or C == 0:
+                return best_val, best_idx.to(torch.int64)
+            # columns in the order of their gallery positions: the merge kernel's tie rule (smaller column) is then the index's
+            by_pos, order = torch.sort(positions.long(), dim=1, stable=True)
+            ops.topk_merge(scores.gather(1, order), 0, 0, best_val, best_idx)
+            pos = by_pos.gather(1, best_idx.long().clamp_(min=0))
+            pos = torch.where(best_idx >= 0, pos, torch.full_like(pos, -1))
+        return best_val, self._ids_of(pos)
+
+    def _ids_of(self, pos):
+        """gallery positions [.., k] int64 (-1 = none) -> ids"""
+        if self._running_ids:
+            return pos
+        found = self._ids[:self._n][pos.clamp(min=0)]
+        return torch.where(pos >= 0, found, torch.full_like(found, -1))
+
+    def _search_two_stage(self, features, tokens, k, C):
+        self._refuse_rerank("search(candidates=C)")
+        if not 1 <= k <= C <= ops.TOPK_MAX_K:
+            raise ValueError(f"LateInteractionIndex.search: candidates must satisfy k <= C <= {ops.TOPK_MAX_K} (got k = {k}, C = {C})")
+        if tokens is None or not self._tok and self._n:
+            raise ValueError("LateInteractionIndex.search: alpha != 1 needs token features on both sides")
+        nq = features.shape[0]
+        dev = self.device
+        features = features.detach().to(dev).float().contiguous()
+        cand_val, cand_idx = ops.topk_init(nq, C, dev)
+        if nq == 0 or self._n == 0:
+            best_val, best_idx = ops.topk_init(nq, k, dev)
+            return best_val, best_idx.to(torch.int64)
+        gallery_is_image = self.kind == "image"
+        qchunk = min(max(1, int(self.QUERY_CHUNK)), nq)
+        from .train import similarity_matrix
+        with torch.no_grad():
+            for q0 in range(0, nq, qchunk):                      # stage 1: the C best by the global similarity
+                q1 = min(nq, q0 + qchunk)
+                for base, gf, _ in self.chunks():
+                    G = similarity_matrix(gf, features[q0:q1]) if gallery_is_image else similarity_matrix(features[q0:q1], gf)
+                    ops.topk_merge(G, 1 if gallery_is_image else 0, base, cand_val[q0:q1], cand_idx[q0:q1])
+        return self.rerank(features, tokens, cand_idx, k, global_scores=cand_val)     # stage 2
+
     # ------------------------------------------------------------------ through a model
     @classmethod
     def from_model(cls, model, kind, alpha=None, device=None, token_dtype=None):
@@ -318,10 +443,10 @@ class LateInteractionIndex:
             raise ValueError(f"LateInteractionIndex: this index holds {self.kind}s")
         return self.add(*self._encode(model, what, batch), ids=ids)
 
-    def _search_encoded(self, model, what, batch, k):
+    def _search_encoded(self, model, what, batch, k, candidates=None):
         if self.kind == what:
             raise ValueError(f"LateInteractionIndex: an index of {self.kind}s is queried with the other side")
-        return self.search(*self._encode(model, what, batch), k)
+        return self.search(*self._encode(model, what, batch), k, candidates=candidates)
 
     def add_images(self, model, images, ids=None):
         return self._add_encoded(model, "image", images, ids)
@@ -329,11 +454,11 @@ class LateInteractionIndex:
     def add_texts(self, model, texts, ids=None):
         return self._add_encoded(model, "text", texts, ids)
 
-    def search_texts(self, model, texts, k):
-        return self._search_encoded(model, "text", texts, k)
+    def search_texts(self, model, texts, k, candidates=None):
+        return self._search_encoded(model, "text", texts, k, candidates)
 
-    def search_images(self, model, images, k):
-        return self._search_encoded(model, "image", images, k)
+    def search_images(self, model, images, k, candidates=None):
+        return self._search_encoded(model, "image", images, k, candidates)
 
     # ------------------------------------------------------------------ files
     def save(self, path):
@@ -422,6 +547,9 @@ def build_parser():
     parser.add_argument("--index-dtype", choices=["model", "fp8"], default="model",
                         help="token storage of a new index: the model's compute dtype, or e4m3 bytes + one exponent per token "
                              "(half the bytes, scored on the fp8 MFMA); --load-index takes it from the saved meta.json")
+    parser.add_argument("--candidates", type=int, default=0,
+                        help="0: score every gallery item (exhaustive).  C >= --k: two stages, the C best items per query by the "
+                             "global similarity, then the full late-interaction score of those only")
     return parser
 
 
@@ -431,6 +559,13 @@ def parse_args(argv):
         raise SystemExit("--save-index and --load-index exclude each other")
     if not 1 <= args.k <= ops.TOPK_MAX_K:
         raise SystemExit(f"--k must be in 1 .. {ops.TOPK_MAX_K}")
+    if args.candidates:
+        if not args.k <= args.candidates <= ops.TOPK_MAX_K:
+            raise SystemExit(f"--candidates must be 0 (exhaustive) or in --k .. {ops.TOPK_MAX_K}")
+        if args.index_dtype == "fp8":
+            raise SystemExit("--candidates reranks bf16 / fp32 tokens; it excludes --index-dtype fp8")
+        if getattr(args, "evaluate_as_original_clip", False):
+            raise SystemExit("--candidates excludes --evaluate-as-original-clip: with alpha = 1 the exact search is already the global one")
     return args
 
 
@@ -493,7 +628,7 @@ def run(args):
             index.save(args.save_index)
     scores, found, query_ids = [], [], []
     for batch, ids in queries():
-        s, i = index._search_encoded(model, other, batch, args.k)
+        s, i = index._search_encoded(model, other, batch, args.k, candidates=args.candidates or None)
         scores.append(s)
         found.append(i)
         query_ids.append(ids)

@@ -483,6 +483,24 @@ int clipx_maxsim_scatter_packed(int R, int r0, int ld, int ni, int q, const int*
 int clipx_maxsim_scale_rows(int R, int e, const float* row_w, const void* x, void* y, void* stream);
 int clipx_maxsim_expand(int dtype, int nt, int n_tok, int e, const int* cu, const float* dpacked, void* dtxt, void* stream);
 
+/* ---- gathered MaxSim for reranking (csrc/maxsim_pairs.hip; LateInteractionIndex.rerank) -----------------------------
+ * out[i * ld_out + c] = scale * (alpha * Gp[i * ld_gp + c] + beta * MaxSim(pair)) for query i < nq and candidate slot c < C, the
+ * pair being query i and gallery position p = cand[i * C + c]; p == -1 writes -inf and reads no token.  Gp == NULL: no global term.
+ * gallery_is_image != 0: queries are texts [nq, n, e] bf16 with query_cnt [nq] (clipx_maxsim_pack_text's cnt), the gallery holds
+ * images [.., q, e]; == 0: queries are images [nq, q, e], the gallery holds texts [.., n, e] with their cnt.  The gallery is
+ * the index's chunked storage as it is: gal_tok is a DEVICE table of n_chunks base addresses of [chunk_items, q or n, e] bf16
+ * tensors, gal_cnt (text gallery) one of [chunk_items] int32 tensors; position p is item p % chunk_items of chunk p / chunk_items.
+ * MaxSim is the arithmetic of clipx_maxsim_score_fold on the first cnt rows of the text, row cnt - 1 weighted n - cnt + 1.
+ * status: 4 bytes of device scratch.  Refused, with nothing scored and `out` untouched: q < 16, e % 64 != 0, e < 128, a query side
+ * of more than 80 rows (image gallery: n, text gallery: q) or 128 KiB of staging (16-padded rows x (e + 8) x 2 bytes), C > 524280,
+ * cand_stride != C, ld_out or ld_gp < C, n_items > n_chunks * chunk_items, and -- found by one read-only pass over cand and the
+ * cnt it names, which costs a stream synchronisation -- a position outside [0, n_items) other than -1 or a cnt outside 1 .. n.
+ * nq == 0 or C == 0 launches nothing.                                                                                          */
+int clipx_maxsim_pairs(int gallery_is_image, int nq, int C, int q, int n, int e, const void* query, const int* query_cnt,
+                       const void* gal_tok, const void* gal_cnt, int n_chunks, int chunk_items, long n_items, const int* cand,
+                       long cand_stride, const float* Gp, long ld_gp, float* out, long ld_out, float alpha, float beta, float scale,
+                       int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
